@@ -10,7 +10,7 @@ exactly this, ToucanTTSInterface.py:139-141).  Inputs are resident in HBM before
 Prints ONE JSON line on rank 0.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--phones 128] [--vocoder bigvgan|hifigan]
-                    [--dtype fp32|bf16|fp16] [--pitch-scale S] [--energy-scale S] [--no-cpu-baseline]
+                    [--dtype fp32|bf16|fp16] [--pitch-scale S] [--energy-scale S] [--no-cpu-baseline] [--dump-outputs DIR]
 
   --dtype bf16 (default)                                    BASELINE.json configs[2]
   --dtype fp16 --pitch-scale 1.3 --energy-scale 0.7         the per-GPU shard of configs[4] (fp16 MFMA, PostFlow on, variance scaling)
@@ -62,7 +62,13 @@ def parse_args():
     ap.add_argument("--sequencer", default="native", choices=["native", "python"],
                     help="native: the stage API (csrc/pipeline.hip sequences the kernels in C++; the product path); python: engine.py issues "
                          "every kernel-level call itself")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (rank 0's utterances) to DIR/<name>.npy, float32 / float64, at most "
+                         "64 MB in all: see dump_outputs()")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def relaunch_distributed(args):
@@ -217,6 +223,44 @@ def verify_against_single_run(pipe, out, wav, packed, z_sq, scales, B, oracle=No
                                        "mel_mean_abs": float(mel_o.abs().mean()), "wav_mean_abs_err": float((wav_b - wav_o).abs().mean()),
                                        "wav_max_abs_err": float((wav_b - wav_o).abs().max()), "wav_mean_abs": float(wav_o.abs().mean())}
     return v
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def outputs_to_host(out, wav):
+    """The arrays a caller of the timed path receives, utterance after utterance (the packed tensors' alignment rows between
+    utterances are not outputs and are left out), copied to the host: mel [frames, 80], wav [frames * 384] (384 samples per
+    mel frame), durations / pitch / energy [phonemes], frames_per_utterance [B].  Called right after the timed region: with
+    --graphs the tensors are views of graph-owned buffers that the next call overwrites."""
+    import numpy as np
+    import torch
+    rag = out["rag_mel"]
+    cat = lambda ts: torch.cat([t.reshape(-1) for t in ts]).cpu().numpy().astype(np.float32)
+    return {"mel": torch.cat(out["mel"]).cpu().numpy().astype(np.float32),
+            "wav": cat([wav[384 * b0:384 * (b0 + n)] for b0, n in zip(rag.begins, rag.lengths)]),
+            "durations": cat(out["durations"]), "pitch": cat(out["pitch"]), "energy": cat(out["energy"]),
+            "frames_per_utterance": np.array(rag.lengths, dtype=np.float64)}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array of outputs_to_host().  When mel and wav together would take the total past
+    DUMP_LIMIT_BYTES, both keep the same fixed sample of frames (rows of mel, their 384 samples of wav), drawn with
+    numpy.random.default_rng(DUMP_SAMPLE_SEED) and sorted; DIR/sampled_frames.npy then holds the frame indices (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    frames = arrays["mel"].shape[0]
+    frame_bytes = 4 * (80 + 384)
+    rest = sum(a.nbytes for k, a in arrays.items() if k not in ("mel", "wav")) + 128 * (len(arrays) + 1)  # (+ the .npy headers)
+    if rest + frames * frame_bytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - rest) // (frame_bytes + 8)  # (8: the float64 index of a kept frame)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(frames, size=keep, replace=False))
+        arrays = dict(arrays, mel=arrays["mel"][rows], wav=arrays["wav"].reshape(frames, 384)[rows].reshape(-1),
+                      sampled_frames=rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def algorithmic_flops_per_utterance(L, T, vocoder):
@@ -415,6 +459,7 @@ def main():
         tt = torch.tensor([elapsed], device="cpu" if rehearsal else dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    dumped = outputs_to_host(out, wav) if args.dump_outputs and rank == 0 else None
     dom_summary = None
     if use_native:
         if dominant:
@@ -551,6 +596,8 @@ def main():
         if use_native and not args.no_verify:
             log("verify: utterance 0 of the last timed step against a B = 1 run" + (" and the CPU oracle" if oracle_out else ""))
             line["verify"] = verify_against_single_run(pipe, last_out, last_wav, packed, z_sq, scales, B, oracle_out)
+        if dumped is not None:
+            log(f"outputs of the last timed step -> {args.dump_outputs}: {', '.join(dump_outputs(args.dump_outputs, dumped))}")
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()
