@@ -101,37 +101,59 @@ __global__ __launch_bounds__(64) void l2norm_kernel(const float* __restrict__ x,
 // The statistics are a time-axis reduction, so they MUST be per utterance (padding may never leak in).
 // Two launches over a (16-frame chunk, utterance) grid, thread = channel (c <= 256, whole rows = contiguous segments; 64-frame
 // chunks until round 3: 10 workgroups for the 640 frames of a batch-1 pass, 16 + 21 us per norm):
-//   1. partial (sum, sum of squares) per (utterance, chunk, group) into a workspace - no atomics, so the result is
-//      bit-reproducible from run to run and across ranks;
-//   2. every workgroup adds the partials of its utterance in chunk order (fp64), then normalises its own 16 frames.
+//   1. partial (mean, centred M2) per (utterance, chunk, group) into a workspace, two-pass over the chunk's 16 x cpg values - no
+//      atomics, so the result is bit-reproducible from run to run and across ranks;
+//   2. every workgroup combines the partials of its utterance in chunk order (fp64, Chan et al.'s parallel form
+//      M2 = sum M2_k + sum n_k (mean_k - mean)^2), then normalises its own 16 frames.
+// Nothing subtracts two large sums: a one-pass sum of squares in fp32 loses ~mean^2 / var of its bits (a group mean of 300 at unit
+// spread left 1e-2 of error in the output).  All statistics are of x - pivot, the pivot being the utterance's first value of the
+// group, so an fp32 chunk mean is exact to the spread's last bits rather than the offset's (1.5e-5 absolute at an offset of 300).
 constexpr int GN_CHUNK = 16;
 
 __global__ __launch_bounds__(256) void groupnorm_partial_kernel(const float* __restrict__ x, int ldx, int c, int groups,
                                                                 const int* __restrict__ seq_begin, const int* __restrict__ seq_end,
                                                                 float* __restrict__ ws, int n_chunks) {
-  __shared__ float rs[256], rq[256];
+  __shared__ float red[256], gmean[256];
   const int u = blockIdx.y, chunk = blockIdx.x;
-  const int r0 = seq_begin[u] + chunk * GN_CHUNK;
+  const int sb = seq_begin[u];
+  const int r0 = sb + chunk * GN_CHUNK;
   const int r1 = min(seq_end[u], r0 + GN_CHUNK);
-  const int ch = threadIdx.x, cpg = c / groups;
-  float s = 0.f, q = 0.f;
-  if (ch < c)
-    for (int r = r0; r < r1; ++r) {
-      const float v = x[(size_t)r * ldx + ch];
-      s += v;
-      q = fmaf(v, v, q);
+  if (r0 >= r1) return;  // (chunk past the end of this utterance: never read)
+  const int ch = threadIdx.x, cpg = c / groups, g = ch / cpg;
+  float d[GN_CHUNK];
+  float s = 0.f;
+  if (ch < c) {
+    const float pivot = x[(size_t)sb * ldx + g * cpg];
+#pragma unroll
+    for (int i = 0; i < GN_CHUNK; ++i) {
+      d[i] = r0 + i < r1 ? x[(size_t)(r0 + i) * ldx + ch] - pivot : 0.f;
+      s += d[i];
     }
-  rs[ch] = s;
-  rq[ch] = q;
+  }
+  red[ch] = s;
   __syncthreads();
   if (ch < groups) {
-    float gs = 0.f, gq = 0.f;
-    for (int k = 0; k < cpg; ++k) {
-      gs += rs[ch * cpg + k];
-      gq += rq[ch * cpg + k];
+    float gs = 0.f;
+    for (int k = 0; k < cpg; ++k) gs += red[ch * cpg + k];
+    gmean[ch] = gs / (float)((r1 - r0) * cpg);
+  }
+  __syncthreads();
+  float q = 0.f;
+  if (ch < c) {
+    const float m = gmean[g];
+#pragma unroll
+    for (int i = 0; i < GN_CHUNK; ++i) {
+      const float e = r0 + i < r1 ? d[i] - m : 0.f;
+      q = fmaf(e, e, q);
     }
+  }
+  red[ch] = q;
+  __syncthreads();
+  if (ch < groups) {
+    float gq = 0.f;
+    for (int k = 0; k < cpg; ++k) gq += red[ch * cpg + k];
     float* w = ws + (((size_t)u * n_chunks + chunk) * groups + ch) * 2;
-    w[0] = gs;
+    w[0] = gmean[ch];
     w[1] = gq;
   }
 }
@@ -149,21 +171,22 @@ __global__ __launch_bounds__(256) void groupnorm_apply_kernel(const float* __res
   const int ch = threadIdx.x;
   if (ch >= c) return;
   const int cpg = c / groups, g = ch / cpg;
-  const int used = (se - sb + GN_CHUNK - 1) / GN_CHUNK;  // chunks that hold frames of this utterance
-  double s = 0.0, q = 0.0;
+  const int len = se - sb, used = (len + GN_CHUNK - 1) / GN_CHUNK;  // chunks that hold frames of this utterance
+  const float* wg = ws + ((size_t)u * n_chunks * groups + g) * 2;   // chunk k's partial of group g: wg[2 * groups * k + {0, 1}]
+  double s = 0.0;
+  for (int k = 0; k < used; ++k) s += (double)min(GN_CHUNK, len - k * GN_CHUNK) * (double)wg[(size_t)2 * groups * k];
+  const double mean = s / (double)len;  // (of x - pivot; every chunk's count carries the same factor cpg)
+  double m2 = 0.0;
   for (int k = 0; k < used; ++k) {
-    const float* w = ws + (((size_t)u * n_chunks + k) * groups + g) * 2;
-    s += (double)w[0];
-    q += (double)w[1];
+    const double dm = (double)wg[(size_t)2 * groups * k] - mean;
+    m2 += (double)wg[(size_t)2 * groups * k + 1] + (double)(cpg * min(GN_CHUNK, len - k * GN_CHUNK)) * dm * dm;
   }
-  const double cnt = (double)cpg * (double)(se - sb);
-  const double mean = s / cnt;
-  double var = q / cnt - mean * mean;
-  var = var < 0.0 ? 0.0 : var;
+  const double var = m2 / ((double)cpg * (double)len);
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float ga = gamma[ch] * rstd, be = beta[ch] - (float)mean * ga;
+  const float pivot = x[(size_t)sb * ldx + g * cpg], mf = (float)mean;
+  const float ga = gamma[ch] * rstd, be = beta[ch];
   for (int r = r0; r < r1; ++r) {
-    float v = fmaf(x[(size_t)r * ldx + ch], ga, be);
+    float v = fmaf((x[(size_t)r * ldx + ch] - pivot) - mf, ga, be);
     if (apply_tanh) v = tanhf(v);
     if (res) v += res[(size_t)r * ld_res + ch];
     y[(size_t)r * ldy + ch] = v;

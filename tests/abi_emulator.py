@@ -374,10 +374,15 @@ class Emulator:
 
     def tts_layernorm(self, x, ldx, y, ldy, gamma, beta, rows, c, eps, stream):
         self._count("layernorm")
-        X = _mat(x, rows, c, ldx).astype(np.float64)
+        # rows never written by the caller (the padding rows of a ragged batch are torch.empty) may hold NaN / inf bit patterns -
+        # signalling NaNs raise "invalid value" in the widening cast: such rows are masked and come out as NaN, as on the GPU
+        X = _mat(x, rows, c, ldx)
+        bad = ((X.view(np.uint32) & 0x7F800000) == 0x7F800000).any(1)
+        X = np.where(bad[:, None], np.float32(0), X).astype(np.float64)
         m = X.mean(1, keepdims=True)
         v = ((X - m) ** 2).mean(1, keepdims=True)
         out = (X - m) / np.sqrt(v + eps) * _arr(gamma, c) + _arr(beta, c)
+        out[bad] = np.nan
         _mat(y, rows, c, ldy)[:] = out.astype(np.float32)
         return 0
 
