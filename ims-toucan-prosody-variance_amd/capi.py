@@ -162,7 +162,7 @@ PROTOTYPES = {
 }
 
 _LIB = None
-ABI_VERSION = 14  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
+ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
 
 class ToucanHipError(RuntimeError):

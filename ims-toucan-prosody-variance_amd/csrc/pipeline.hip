@@ -18,7 +18,7 @@
 #include <cstring>
 #include <string>
 #include <unordered_map>
-#include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -94,19 +94,24 @@ struct TileTab {
   int n = 0;
 };
 
-// Tile tables / utterance bounds of ONE batch's group of stages (acoustic stages, or the vocoder): pinned host staging and the device
-// copy, filled by asynchronous copies on the group's stream - no device allocation, no synchronisation per table.  Two generations
-// per group alternate from batch to batch.
-struct TableArena {
+// Tile tables / utterance bounds of a group of stages (acoustic stages, or the vocoder) in one of its two generations, which
+// alternate from batch to batch.  Append-only: a table is copied into pinned staging and uploaded with one asynchronous copy on the
+// stage's stream, into a chunk that is never moved or freed before tts_destroy - an address handed out stays valid.  A generation
+// keeps its tables from batch to batch (a repeating layout is found, not uploaded again) until it holds more than TABLE_BUDGET bytes:
+// then the next batch that takes it rewinds it, once its last use has completed.
+constexpr size_t TABLE_FIRST_CHUNK = 64 << 10;
+constexpr size_t TABLE_BUDGET = 16 << 20;
+
+struct TableChunk {
   char* dev = nullptr;
-  char* host = nullptr;
+  char* host = nullptr;  // staging, same size
   size_t cap = 0, off = 0;
-  hipEvent_t copied = nullptr;   // recorded behind the generation's latest copy: the staging bytes may be rewritten once it has passed
-  hipEvent_t fence = nullptr;    // (reuse from another stream) everything enqueued on the previous stream when the arena is taken again
-  bool armed = false;
-  hipStream_t stream = nullptr;  // the stream the generation's copies and kernels were enqueued on
-  std::unordered_map<std::string, TileTab> tiles;
-  std::unordered_map<std::string, int*> bounds;
+};
+
+struct TableStore {
+  std::vector<TableChunk> chunks;
+  std::unordered_map<std::string, std::pair<void*, int>> index;  // layout key -> device address, element count
+  hipEvent_t last_use = nullptr;  // recorded on its stream at the end of every stage entry of the group (the extern "C" wrappers)
 };
 
 // one timed launch of the roofline leg (tts_profile): HIP events on the launch stream around a matrix-core kernel
@@ -122,17 +127,11 @@ struct Handle {
   TtsConfig cfg;
   std::unordered_map<std::string, Dev> weights;
   bool resolved = false;
-  Arena phone, frame, voc[2], tables;
-  // tables of layouts that keep coming back (a benchmark's fixed batch): device allocations of their own, kept.  A layout is
-  // built into the batch's TableArena the first time it is seen and moves here the second time (real traffic - new utterance
-  // lengths every batch - never allocates or synchronises for a table).
-  std::unordered_map<std::string, TileTab> tile_cache;
-  std::unordered_map<std::string, int*> bounds_cache;
-  std::unordered_set<std::string> seen_once;
-  TableArena tabs[2][2];          // [0: acoustic stages, 1: vocoder][generation]
+  Arena phone, frame, voc[2];
+  TableStore tabs[2][2];          // [0: acoustic stages, 1: vocoder][generation]
   int tab_gen[2] = {0, 0};
   int tab_which = 0;              // group of the stage entry that runs (set with split_mode)
-  long long n_arena_tables = 0, n_cached_tables = 0;  // tables built into a batch arena / given a permanent allocation (tts_table_stats)
+  long long n_tables_built = 0;   // (tts_table_stats)
   int small_tile_blocks = 1536;
   int split_mode = 0;             // set by the stage entries; the fp32 configuration only.  2 (phoneme stages: encoder, predictors): split-K convs
                                   // and key-split attention at EVERY grid size - durations are a rounding of exp(log d), so everything upstream
@@ -209,7 +208,7 @@ T* arena_alloc(Arena& a, size_t count) {
     return TTS_E_ARG;                                                                          \
   }
 
-// ---- tile tables and utterance bounds (cached per layout signature) ---------------------------------------------------
+// ---- tile tables and utterance bounds (kept per layout signature) -----------------------------------------------------
 std::string layout_key(const Layout& l, int tile_rows) {
   std::string k(reinterpret_cast<const char*>(l.begins.data()), l.begins.size() * sizeof(int));
   k.append(reinterpret_cast<const char*>(l.lengths.data()), l.lengths.size() * sizeof(int));
@@ -217,149 +216,91 @@ std::string layout_key(const Layout& l, int tile_rows) {
   return k;
 }
 
-void drop_tables(Handle* h) {
-  for (auto& kv : h->tile_cache) (void)hipFree(kv.second.dev);
-  for (auto& kv : h->bounds_cache) (void)hipFree(kv.second);
-  h->tile_cache.clear();
-  h->bounds_cache.clear();
-}
-
 // a stage group starts a batch: take the group's other table generation
 int tables_begin(Handle* h, int which, hipStream_t st) {
   h->tab_which = which;
   h->tab_gen[which] ^= 1;
-  TableArena& a = h->tabs[which][h->tab_gen[which]];
-  if (a.armed) {
-    // the staging bytes of the batch before last: its copies have long run unless the host is more than two batches ahead of the GPU
-    TTS_TRY(hip_ok(hipEventSynchronize(a.copied), "tile tables: staging buffer still in flight"));
-    if (a.stream != st) {  // its kernels ran on another stream: order this batch's copies behind everything enqueued there
-      TTS_TRY(hip_ok(hipEventRecord(a.fence, a.stream), "tile tables: fence"));
-      TTS_TRY(hip_ok(hipStreamWaitEvent(st, a.fence, 0), "tile tables: fence wait"));
-    }
+  TableStore& s = h->tabs[which][h->tab_gen[which]];
+  if (!s.last_use) return TTS_OK;  // (never used)
+  size_t held = 0;
+  for (const TableChunk& c : s.chunks) held += c.off;
+  if (held > TABLE_BUDGET) {  // rewind: its staging and device bytes are overwritten from here on
+    TTS_TRY(hip_ok(hipEventSynchronize(s.last_use), "tile tables: last use before rewinding"));
+    s.index.clear();
+    for (TableChunk& c : s.chunks) c.off = 0;
+    return TTS_OK;
   }
-  a.off = 0;
-  a.stream = st;
-  a.tiles.clear();
-  a.bounds.clear();
-  return TTS_OK;
+  const hipError_t q = hipEventQuery(s.last_use);
+  if (q == hipSuccess) return TTS_OK;
+  if (q != hipErrorNotReady) return hip_ok(q, "tile tables: last use");
+  (void)hipGetLastError();  // (not-ready is no error: clear it for the launch checks that follow)
+  // the tables kept in this generation may have been uploaded on another stream: order this batch behind their last use
+  return hip_ok(hipStreamWaitEvent(st, s.last_use, 0), "tile tables: wait for last use");
 }
 
-// bytes -> the current generation of the running group (staging copy + one asynchronous upload); *dev_out: the device address
-int table_put(Handle* h, const void* data, size_t bytes, hipStream_t st, void** dev_out) {
-  TableArena& a = h->tabs[h->tab_which][h->tab_gen[h->tab_which]];
-  const size_t need = (bytes + 255) & ~(size_t)255;
-  if (a.off + need > a.cap) {  // (rare: the first batches, or a batch far larger than any before)
-    // tables already handed out from this generation are still referenced by launches in flight: nothing may be freed under them
-    TTS_TRY(hip_ok(hipDeviceSynchronize(), "tile tables: sync before regrowth"));
-    const size_t cap = std::max<size_t>(std::max<size_t>(a.cap * 2, a.off + need), (size_t)4 << 20);
-    char *dev = nullptr, *host = nullptr;
-    TTS_TRY(hip_ok(hipMalloc(reinterpret_cast<void**>(&dev), cap), "tile tables: hipMalloc"));
-    TTS_TRY(hip_ok(hipHostMalloc(reinterpret_cast<void**>(&host), cap, hipHostMallocDefault), "tile tables: hipHostMalloc"));
-    if (a.off) {
-      memcpy(host, a.host, a.off);
-      TTS_TRY(hip_ok(hipMemcpy(dev, a.dev, a.off, hipMemcpyDeviceToDevice), "tile tables: regrowth copy"));
-      // (tables of this generation handed out before the regrowth keep their old addresses: rebuild the maps' pointers)
-      for (auto& kv : a.tiles) kv.second.dev = reinterpret_cast<TtsTile*>(dev + (reinterpret_cast<char*>(kv.second.dev) - a.dev));
-      for (auto& kv : a.bounds) kv.second = reinterpret_cast<int*>(dev + (reinterpret_cast<char*>(kv.second) - a.dev));
+// the table `key` of the running group's current generation.  On a miss build() makes its host elements, which are appended:
+// into the first chunk with room, else into a new one twice the size of the last (one staging copy + one upload on st)
+template <class Build>
+int table_of(Handle* h, const std::string& key, hipStream_t st, Build build, void** dev, int* n) {
+  TableStore& s = h->tabs[h->tab_which][h->tab_gen[h->tab_which]];
+  auto it = s.index.find(key);
+  if (it == s.index.end()) {
+    auto host = build();
+    const int count = (int)host.size();
+    if (host.empty()) host.resize(1);  // (an empty layout still gets a valid address)
+    const size_t bytes = host.size() * sizeof(host[0]), need = (bytes + 255) & ~(size_t)255;
+    TableChunk* c = nullptr;
+    for (TableChunk& k : s.chunks)
+      if (k.off + need <= k.cap) {
+        c = &k;
+        break;
+      }
+    if (!c) {
+      TableChunk k;
+      k.cap = std::max(s.chunks.empty() ? TABLE_FIRST_CHUNK : 2 * s.chunks.back().cap, need);
+      TTS_TRY(hip_ok(hipMalloc(reinterpret_cast<void**>(&k.dev), k.cap), "tile tables: hipMalloc"));
+      const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&k.host), k.cap, hipHostMallocDefault);
+      if (e != hipSuccess) (void)hipFree(k.dev);
+      TTS_TRY(hip_ok(e, "tile tables: hipHostMalloc"));
+      s.chunks.push_back(k);
+      c = &s.chunks.back();
     }
-    if (a.dev) (void)hipFree(a.dev);
-    if (a.host) (void)hipHostFree(a.host);
-    a.dev = dev; a.host = host; a.cap = cap;
+    memcpy(c->host + c->off, host.data(), bytes);
+    TTS_TRY(hip_ok(hipMemcpyAsync(c->dev + c->off, c->host + c->off, bytes, hipMemcpyHostToDevice, st), "tile tables: upload"));
+    it = s.index.emplace(key, std::make_pair(static_cast<void*>(c->dev + c->off), count)).first;
+    c->off += need;
+    ++h->n_tables_built;
   }
-  if (!a.copied) {
-    TTS_TRY(hip_ok(hipEventCreateWithFlags(&a.copied, hipEventDisableTiming), "tile tables: event"));
-    TTS_TRY(hip_ok(hipEventCreateWithFlags(&a.fence, hipEventDisableTiming), "tile tables: event"));
-  }
-  memcpy(a.host + a.off, data, bytes);
-  TTS_TRY(hip_ok(hipMemcpyAsync(a.dev + a.off, a.host + a.off, bytes, hipMemcpyHostToDevice, st), "tile tables: upload"));
-  TTS_TRY(hip_ok(hipEventRecord(a.copied, st), "tile tables: event record"));
-  a.armed = true;
-  *dev_out = a.dev + a.off;
-  a.off += need;
+  *dev = it->second.first;
+  if (n) *n = it->second.second;
   return TTS_OK;
-}
-
-// first sighting of a layout: build into the batch arena; second sighting: it is a repeating layout - give it a permanent table
-bool repeating(Handle* h, const std::string& key) {
-  if (h->seen_once.count(key)) return true;
-  if (h->seen_once.size() > 8192) h->seen_once.clear();
-  h->seen_once.insert(key);
-  return false;
 }
 
 int tiles_of(Handle* h, const Layout& l, int tile_rows, hipStream_t st, TileTab* out) {
-  const std::string key = layout_key(l, tile_rows);
-  auto it = h->tile_cache.find(key);
-  if (it != h->tile_cache.end()) {
-    *out = it->second;
-    return TTS_OK;
-  }
-  TableArena& a = h->tabs[h->tab_which][h->tab_gen[h->tab_which]];
-  auto ia = a.tiles.find(key);
-  if (ia != a.tiles.end()) {
-    *out = ia->second;
-    return TTS_OK;
-  }
-  std::vector<TtsTile> host;
-  for (int u = 0; u < l.n(); ++u)
-    for (int r = 0; r < l.lengths[u]; r += tile_rows) host.push_back(TtsTile{l.begins[u] + r, l.begins[u], l.begins[u] + l.lengths[u], u});
-  TileTab t;
-  t.n = (int)host.size();
-  if (!repeating(h, key)) {
-    if (host.empty()) host.push_back(TtsTile{0, 0, 0, 0});
-    void* dev;
-    TTS_TRY(table_put(h, host.data(), host.size() * sizeof(TtsTile), st, &dev));
-    t.dev = static_cast<TtsTile*>(dev);
-    a.tiles[key] = t;
-    ++h->n_arena_tables;
-    *out = t;
-    return TTS_OK;
-  }
-  if (h->tile_cache.size() > 512) {  // (no launch in flight may still read a table - on this stream or, when the caller runs the
-                                     // vocoder of one batch beside the acoustic model of the next, on another: drain the device first)
-    TTS_TRY(hip_ok(hipDeviceSynchronize(), "tile tables: sync before trimming the cache"));
-    drop_tables(h);
-  }
-  TTS_TRY(hip_ok(hipMalloc(reinterpret_cast<void**>(&t.dev), std::max<size_t>(1, host.size()) * sizeof(TtsTile)), "tile table: hipMalloc"));
-  if (!host.empty())
-    TTS_TRY(hip_ok(hipMemcpyAsync(t.dev, host.data(), host.size() * sizeof(TtsTile), hipMemcpyHostToDevice, st), "tile table: upload"));
-  TTS_TRY(hip_ok(hipStreamSynchronize(st), "tile table: upload sync"));  // (the host vector goes out of scope; once per repeating layout)
-  h->tile_cache[key] = t;
-  ++h->n_cached_tables;
-  *out = t;
+  void* dev;
+  TTS_TRY(table_of(h, layout_key(l, tile_rows), st, [&] {
+    std::vector<TtsTile> host;
+    for (int u = 0; u < l.n(); ++u)
+      for (int r = 0; r < l.lengths[u]; r += tile_rows) host.push_back(TtsTile{l.begins[u] + r, l.begins[u], l.begins[u] + l.lengths[u], u});
+    return host;
+  }, &dev, &out->n));
+  out->dev = static_cast<TtsTile*>(dev);
   return TTS_OK;
 }
 
 // (seq_begin[n] | seq_end[n]) device array
 int bounds_of(Handle* h, const Layout& l, hipStream_t st, const int** sb, const int** se) {
-  const std::string key = layout_key(l, -1);
-  auto it = h->bounds_cache.find(key);
-  int* dev = nullptr;
-  TableArena& a = h->tabs[h->tab_which][h->tab_gen[h->tab_which]];
-  if (it != h->bounds_cache.end()) {
-    dev = it->second;
-  } else if (a.bounds.count(key)) {
-    dev = a.bounds[key];
-  } else {
+  void* dev;
+  TTS_TRY(table_of(h, layout_key(l, -1), st, [&] {
     std::vector<int> host(2 * std::max(1, l.n()));
     for (int u = 0; u < l.n(); ++u) {
       host[u] = l.begins[u];
       host[l.n() + u] = l.begins[u] + l.lengths[u];
     }
-    if (!repeating(h, key)) {
-      void* p;
-      TTS_TRY(table_put(h, host.data(), host.size() * sizeof(int), st, &p));
-      dev = static_cast<int*>(p);
-      a.bounds[key] = dev;
-    } else {
-      TTS_TRY(hip_ok(hipMalloc(reinterpret_cast<void**>(&dev), host.size() * sizeof(int)), "bounds: hipMalloc"));
-      TTS_TRY(hip_ok(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, st), "bounds: upload"));
-      TTS_TRY(hip_ok(hipStreamSynchronize(st), "bounds: upload sync"));
-      h->bounds_cache[key] = dev;
-    }
-  }
-  *sb = dev;
-  *se = dev + l.n();
+    return host;
+  }, &dev, nullptr));
+  *sb = static_cast<const int*>(dev);
+  *se = *sb + l.n();
   return TTS_OK;
 }
 
@@ -750,13 +691,13 @@ int pipeline_destroy(Handle* h) {
   for (auto& kv : h->weights)
     if (kv.second.dtype != 3 && kv.second.p) (void)hipFree(kv.second.p);
     else free(kv.second.p);
-  drop_tables(h);
   for (auto& group : h->tabs)
-    for (TableArena& t : group) {
-      if (t.dev) (void)hipFree(t.dev);
-      if (t.host) (void)hipHostFree(t.host);
-      if (t.copied) (void)hipEventDestroy(t.copied);
-      if (t.fence) (void)hipEventDestroy(t.fence);
+    for (TableStore& s : group) {
+      for (TableChunk& c : s.chunks) {
+        (void)hipFree(c.dev);
+        (void)hipHostFree(c.host);
+      }
+      if (s.last_use) (void)hipEventDestroy(s.last_use);
     }
   for (Arena* a : {&h->phone, &h->frame, &h->voc[0], &h->voc[1]})
     if (a->base) (void)hipFree(a->base);
@@ -1268,6 +1209,17 @@ int pipeline_vocoder(Handle* h, int kind, const float* mel, int ld_mel, const in
   return tts_conv_post(static_cast<const float*>(x.p), ch, ch, pw, h->cfg.post_bias, TTS_PRE_LRELU, 0.01f, wav, tp.dev, tp.n, 256, xflag, st);  // InferenceAvocodo.py:53
 }
 
+// the end of every stage entry, whatever its outcome (the extern "C" wrappers): the table generation of `group` that the running batch
+// uses was last used on st.  rc: the entry's own status, which comes first
+int stage_done(Handle* h, int group, hipStream_t st, int rc) {
+  if (!h) return rc;
+  TableStore& s = h->tabs[group][h->tab_gen[group]];
+  hipError_t e = hipSuccess;
+  if (!s.last_use && (e = hipEventCreateWithFlags(&s.last_use, hipEventDisableTiming)) != hipSuccess) s.last_use = nullptr;
+  if (e == hipSuccess) e = hipEventRecord(s.last_use, st);
+  return rc != TTS_OK ? rc : hip_ok(e, "tile tables: last use");
+}
+
 }  // namespace tts
 
 // ======================================================================================================================
@@ -1285,26 +1237,32 @@ int64_t tts_workspace_bytes(const TtsHandle* h, int32_t B, int32_t Lmax, int32_t
   return tts::pipeline_workspace_bytes(reinterpret_cast<const tts::Handle*>(h), B, Lmax, Tmax);
 }
 int64_t tts_workspace_claimed(const TtsHandle* h) { return tts::pipeline_workspace_claimed(reinterpret_cast<const tts::Handle*>(h)); }
-int tts_table_stats(const TtsHandle* h, int64_t* arena_tables, int64_t* cached_tables) {
-  if (!h || !arena_tables || !cached_tables) return TTS_E_ARG;
-  *arena_tables = reinterpret_cast<const tts::Handle*>(h)->n_arena_tables;
-  *cached_tables = reinterpret_cast<const tts::Handle*>(h)->n_cached_tables;
+int tts_table_stats(const TtsHandle* h, int64_t* tables_built, int64_t* table_chunks) {
+  if (!h || !tables_built || !table_chunks) return TTS_E_ARG;
+  const tts::Handle* hh = reinterpret_cast<const tts::Handle*>(h);
+  *tables_built = hh->n_tables_built;
+  *table_chunks = 0;
+  for (const auto& group : hh->tabs)
+    for (const tts::TableStore& s : group) *table_chunks += (int64_t)s.chunks.size();
   return TTS_OK;
 }
 int tts_encoder(TtsHandle* h, const float* text, const float* utt_emb, const int32_t* lang_ids, const int32_t* phone_lengths, int32_t B,
                 tts_stream_t stream) {
-  return tts::pipeline_encoder(H(h), text, utt_emb, lang_ids, phone_lengths, B, ST(stream));
+  return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_encoder(H(h), text, utt_emb, lang_ids, phone_lengths, B, ST(stream)));
 }
 int tts_variance_predictors(TtsHandle* h, const float* gold_pitch, const float* gold_energy, const int32_t* gold_durations, tts_stream_t stream) {
-  return tts::pipeline_predictors(H(h), gold_pitch, gold_energy, gold_durations, ST(stream));
+  return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_predictors(H(h), gold_pitch, gold_energy, gold_durations, ST(stream)));
 }
 int tts_control_and_regulate(TtsHandle* h, float duration_scale, float pitch_scale, float energy_scale, float pause_scale,
                              int32_t* frame_counts, tts_stream_t stream) {
-  return tts::pipeline_control_regulate(H(h), duration_scale, pitch_scale, energy_scale, pause_scale, frame_counts, ST(stream));
+  return tts::stage_done(H(h), 0, ST(stream),
+                         tts::pipeline_control_regulate(H(h), duration_scale, pitch_scale, energy_scale, pause_scale, frame_counts, ST(stream)));
 }
-int tts_decoder(TtsHandle* h, tts_stream_t stream) { return tts::pipeline_decoder(H(h), ST(stream)); }
-int tts_postnet(TtsHandle* h, tts_stream_t stream) { return tts::pipeline_postnet(H(h), ST(stream)); }
-int tts_postflow(TtsHandle* h, const float* z_noise, tts_stream_t stream) { return tts::pipeline_postflow(H(h), z_noise, ST(stream)); }
+int tts_decoder(TtsHandle* h, tts_stream_t stream) { return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_decoder(H(h), ST(stream))); }
+int tts_postnet(TtsHandle* h, tts_stream_t stream) { return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_postnet(H(h), ST(stream))); }
+int tts_postflow(TtsHandle* h, const float* z_noise, tts_stream_t stream) {
+  return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_postflow(H(h), z_noise, ST(stream)));
+}
 int tts_mel(TtsHandle* h, const float** mel, int32_t* ld, int32_t* frame_begins, int32_t* frame_counts) {
   return tts::pipeline_mel(H(h), mel, ld, frame_begins, frame_counts);
 }
@@ -1389,11 +1347,11 @@ int tts_copy_mel(TtsHandle* h, float* dst, int32_t ld_dst, tts_stream_t stream) 
 }
 int tts_vocoder_bigvgan(TtsHandle* h, const float* mel, int32_t ld_mel, const int32_t* frame_begins, const int32_t* frame_counts, int32_t B,
                         float* wav, tts_stream_t stream) {
-  return tts::pipeline_vocoder(H(h), 2, mel, ld_mel, frame_begins, frame_counts, B, wav, ST(stream));
+  return tts::stage_done(H(h), 1, ST(stream), tts::pipeline_vocoder(H(h), 2, mel, ld_mel, frame_begins, frame_counts, B, wav, ST(stream)));
 }
 int tts_vocoder_hifigan(TtsHandle* h, const float* mel, int32_t ld_mel, const int32_t* frame_begins, const int32_t* frame_counts, int32_t B,
                         float* wav, tts_stream_t stream) {
-  return tts::pipeline_vocoder(H(h), 1, mel, ld_mel, frame_begins, frame_counts, B, wav, ST(stream));
+  return tts::stage_done(H(h), 1, ST(stream), tts::pipeline_vocoder(H(h), 1, mel, ld_mel, frame_begins, frame_counts, B, wav, ST(stream)));
 }
 
 // The whole pass for one ragged batch.  z_noise == NULL skips the flow (the refined mel is vocoded); wav == NULL skips the vocoder.

@@ -217,7 +217,7 @@ class NativePipeline:
         return sum(int(self.lib.tts_workspace_bytes(handle, B, Lmax, Tmax)) for handle in self._handles())
 
     def table_stats(self):
-        """(tile tables built into batch arenas, tile tables given a permanent allocation) over this pipeline's handles."""
+        """(tile tables built and uploaded, table chunks allocated) over this pipeline's handles (tts_table_stats)."""
         a = b = 0
         for handle in self._handles():
             x, y = C.c_int64(), C.c_int64()

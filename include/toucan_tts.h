@@ -315,7 +315,8 @@ int tts_log10_floor(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t 
  * Stage API: a handle that owns the packed weights and the workspace, and one call per stage of the reference's forward pass
  * (csrc/pipeline.hip sequences the kernels above in C++).  One handle per (process, device); calls on a
  * handle are serialised by the caller's stream.  All pointers are device pointers unless marked host.  Allocation happens only
- * inside the handle (weights, workspace arenas that grow to the largest batch seen, cached tile tables).
+ * inside the handle (weights, workspace arenas that grow to the largest batch seen, the tile tables of its batches: append-only
+ * chunks per stage group, kept until tts_destroy; a layout that comes back is found there, not uploaded again).
  *
  * Mirrors: tts_encoder = Conformer.forward on the phoneme features (Layers/Conformer.py:92-134, InferenceToucanTTS.py:202-206);
  * tts_variance_predictors = VariancePredictor / DurationPredictor (InferenceToucanTTS.py:209-211); tts_control_and_regulate =
@@ -353,10 +354,10 @@ int tts_load_weights(TtsHandle* h, const char* name, const void* host_ptr, const
 int64_t tts_workspace_bytes(const TtsHandle* h, int32_t B, int32_t Lmax, int32_t Tmax);
 /* Bytes the handle's workspace arenas hold right now (after a batch: what that batch - and every larger one before it - claimed). */
 int64_t tts_workspace_claimed(const TtsHandle* h);
-/* Tile tables the handle has built so far: into a batch's table arena (stream-ordered copies, no allocation, no synchronisation:
- * every layout the first time it is seen) / with a permanent device allocation (a layout seen a second time: a benchmark's fixed
- * batch).  Real traffic - new utterance lengths in every batch - only ever counts in the first. */
-int tts_table_stats(const TtsHandle* h, int64_t* arena_tables, int64_t* cached_tables);
+/* *tables_built: tile tables (and utterance bounds) the handle has built and uploaded so far - one per layout that the table
+ * generation of its batch did not hold yet, so a batch that repeats an earlier one builds none.  *table_chunks: table chunks
+ * (device memory + pinned staging of the same size) the handle has allocated. */
+int tts_table_stats(const TtsHandle* h, int64_t* tables_built, int64_t* table_chunks);
 
 /* text: packed phoneme features [sum L, 62]; utt_emb [B, 64] (NULL for the single-speaker variant); lang_ids [B] (NULL: no
  * language embedding); phone_lengths: host [B].  Starts a batch: later stages work on the handle's state. */
@@ -413,7 +414,7 @@ int tts_diag_queue_nonzero(void);
 int tts_diag_queue_slots_used(void);
 /* Bumped whenever a struct layout or a prototype in this header changes; a binding must refuse a library that reports
  * another value (the descriptors are passed by layout, a stale build would read garbage). */
-#define TTS_ABI_VERSION 14
+#define TTS_ABI_VERSION 15
 int tts_abi_version(void);
 
 #ifdef __cplusplus

@@ -114,7 +114,8 @@ def test_bench_path_full_size_bf16_two_streams_equals_the_python_sequencer():
     """BASELINE.json configs[2] at full size the way bench.py runs it: inputs packed once (pack_inputs / squeeze_noise), three steps
     with the acoustic model of step k+1 on one HIP stream beside the vocoder of step k on another (bench.py's step_overlapped
     through the same helper), bf16.  Every step's mel and waveform equal the Python sequencer's (engine.py: the path the golden /
-    oracle parity tests drive) bit for bit, and utterance 0 - the reference golden L128_gold5 - keeps the stated bf16 tolerance."""
+    oracle parity tests drive) bit for bit, and utterance 0 - the reference golden L128_gold5 - keeps the stated bf16 tolerance.  The
+    third step builds no tile table: it takes the table generation the first step filled."""
     import bench
     g = _gold("L128_gold5")
     B, L = 32, 128
@@ -134,8 +135,12 @@ def test_bench_path_full_size_bf16_two_streams_equals_the_python_sequencer():
     packed = pipe.pack_inputs([t.to(dev) for t in texts], embs.to(dev), langs, durations=[d.to(dev) for d in durs])
     z_sq = pipe.squeeze_noise([z.to(dev) for z in zs], [int(d.sum()) for d in durs])
     runner = bench.TwoStreamRunner(pipe, packed, z_sq, {}, dev)
-    results = [runner.step() for _ in range(3)]
+    results, built = [], []
+    for _ in range(3):
+        results.append(runner.step())
+        built.append(pipe.table_stats()[0])
     torch.cuda.synchronize()
+    assert built[2] == built[1], built  # the steady state: the third step finds every table the first one built
     for k, (out, wav) in enumerate(results):
         for u in range(B):
             assert torch.equal(out["mel"][u], ref["mel"][u]), f"step {k} utterance {u}: mel differs from the Python sequencer"
