@@ -161,6 +161,15 @@ PROTOTYPES = {
     "tts_synthesize_batch": (C.c_int, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _f, _f, _f, _f, _p, _p, _p, _p, C.c_int64, C.POINTER(C.c_int64), _p]),
 }
 
+# symbol -> (restype, argtypes); mirrors include/toucan_align.h (the prosody cloner's kernels, csrc/align.hip) one to one
+ALIGN_PROTOTYPES = {
+    "tts_relu_affine": (C.c_int, [_p, _i, _p, _i, _i, _i, _p, _p, _p]),
+    "tts_lstm_recurrence": (C.c_int, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p]),
+    "tts_mas_durations": (C.c_int, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "tts_frame_energy": (C.c_int, [_p, _i, _i, _p, _i, _p]),
+    "tts_token_average": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+}
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -183,7 +192,7 @@ def lib():
     import torch  # noqa: F401
     handle = C.CDLL(LIB_PATH)
     _assert_single_hip_runtime()
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

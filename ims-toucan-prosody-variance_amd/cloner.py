@@ -1,0 +1,89 @@
+"""Drop-in counterpart of InferenceInterfaces/UtteranceCloner.py (:19-194) on the HIP engines: the reference's constructor and
+methods, with the prosody extracted on the GPU (align.py) for one recording or a ragged batch of them.
+
+Stated deviations: the transcript is a phoneme string (no G2P offline); ``on_line_fine_tune=True`` is accepted
+with a one-time warning and not performed (the reference's five SGD steps of CTC training), so the result is that of the
+eval-mode aligner; there is no silero voice-activity trim (the silences are 0 unless ``speech_bounds`` gives the speech span);
+there is no Praat pitch tracker (pitch comes from ``f0=`` or, without it, from the acoustic model given the cloned durations).
+"""
+import os
+import warnings
+
+import torch
+
+from . import align, style
+from . import interface
+from .interface import ToucanTTSInterface, write_wav
+
+
+class UtteranceCloner:
+    _warned_fine_tune = False
+
+    def __init__(self, model_id, device, language="en", speed_over_quality=False):
+        self.tts = ToucanTTSInterface(device=device, tts_model_path=model_id, faster_vocoder=speed_over_quality, language=language)
+        self.device = device
+        self.language = language
+        path = os.path.join(interface.MODELS_DIR, "Aligner", "aligner.pt")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{path}: aligner checkpoint not found (offline, write the fixture one with "
+                                    f"ims_toucan_prosody_variance_amd.interface.write_fixture_aligner_checkpoint)")
+        self.aligner_weights = torch.load(path, map_location="cpu", weights_only=True)["asr_model"]
+        self.extractor = align.ProsodyExtractor(self.aligner_weights, device)
+
+    def _fine_tune_notice(self, on_line_fine_tune):
+        if on_line_fine_tune and not UtteranceCloner._warned_fine_tune:
+            UtteranceCloner._warned_fine_tune = True
+            warnings.warn("on_line_fine_tune=True: the aligner's on-line CTC fine-tuning is not performed; the durations are those of "
+                          "the aligner as loaded (the reference's on_line_fine_tune=False, in eval mode)", stacklevel=3)
+
+    def extract_prosody_batch(self, transcripts, waves, sr, f0=None, speech_bounds=None, on_line_fine_tune=True):
+        """Per utterance (durations, pitch or None, energy, start_silence, end_silence) for phoneme transcripts and recordings at `sr`."""
+        self._fine_tune_notice(on_line_fine_tune)
+        return align.extract_prosody_batch(self.extractor, transcripts, waves, sr, f0=f0, speech_bounds=speech_bounds)
+
+    def extract_prosody(self, transcript, ref_audio_path, lang="de", on_line_fine_tune=True, f0=None, speech_bounds=None):
+        """UtteranceCloner.py:46-145: (duration, pitch, energy, start_silence, end_silence) for one recording.  `lang` only selects
+        the phonemizer in the reference; the transcript here is already phonemes."""
+        self._fine_tune_notice(on_line_fine_tune)
+        wave, sr = style.read_audio(ref_audio_path)
+        return self.extract_prosody_batch([transcript], [wave], sr, f0=None if f0 is None else [f0],
+                                          speech_bounds=None if speech_bounds is None else [speech_bounds], on_line_fine_tune=False)[0]
+
+    def clone_utterance(self, path_to_reference_audio_for_intonation, path_to_reference_audio_for_voice, transcription_of_intonation_reference,
+                        filename_of_result=None, lang="de", f0=None, speech_bounds=None, z_noise=None):
+        """UtteranceCloner.py:147-164: the voice of one recording speaking with the prosody of another."""
+        self.tts.set_utterance_embedding(path_to_reference_audio=path_to_reference_audio_for_voice)
+        duration, pitch, energy, sil_start, sil_end = self.extract_prosody(transcription_of_intonation_reference,
+                                                                           path_to_reference_audio_for_intonation, lang=lang, f0=f0,
+                                                                           speech_bounds=speech_bounds)
+        self.tts.set_language(lang)
+        cloned = self.tts(transcription_of_intonation_reference, view=False, durations=duration, pitch=pitch, energy=energy,
+                          input_is_phones=True, z_noise=z_noise)
+        return self._pad_and_write(cloned, sil_start, sil_end, filename_of_result)
+
+    def biblical_accurate_angel_mode(self, path_to_reference_audio_for_intonation, transcription_of_intonation_reference,
+                                     list_of_speaker_references_for_ensemble, filename_of_result=None, lang="de", f0=None, speech_bounds=None,
+                                     z_noise=None):
+        """UtteranceCloner.py:166-194: several voices with the same prosody, averaged - one batch over the voices."""
+        duration, pitch, energy, sil_start, sil_end = self.extract_prosody(transcription_of_intonation_reference,
+                                                                           path_to_reference_audio_for_intonation, lang=lang, f0=f0,
+                                                                           speech_bounds=speech_bounds)
+        self.tts.set_language(lang)
+        prev = self.tts.default_utterance_embedding.clone()
+        embs = []
+        for p in list_of_speaker_references_for_ensemble:
+            self.tts.set_utterance_embedding(path_to_reference_audio=p)
+            embs.append(self.tts.default_utterance_embedding.clone())
+        self.tts.default_utterance_embedding = prev  # return to normal
+        cloned = self.tts.synthesize_ensemble(transcription_of_intonation_reference, embs, durations=duration, pitch=pitch, energy=energy,
+                                              input_is_phones=True, z_noise=z_noise)
+        return self._pad_and_write(cloned, sil_start, sil_end, filename_of_result)
+
+    def _pad_and_write(self, cloned, sil_start, sil_end, filename):
+        # silences are counted at 16 kHz, the output runs at 48 kHz in the reference's arithmetic: x 3 (UtteranceCloner.py:158-159)
+        start = torch.zeros([sil_start * 3])
+        end = torch.zeros([sil_end * 3])
+        utt = torch.cat((start, cloned.reshape(-1).float().cpu(), end), dim=0).numpy()
+        if filename is not None:
+            write_wav(filename, utt, 24000)
+        return utt

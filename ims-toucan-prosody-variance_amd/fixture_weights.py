@@ -346,3 +346,54 @@ def style_state_dict(seed: int = 8765) -> dict:
 def reference_spectrogram(u: int, frames: int) -> np.ndarray:
     """Seeded stand-in for a log-mel spectrogram [frames, 80] (values in the range log10 mel energies take)."""
     return (normal(f"spec{u}", (frames, N_MEL), 7000 + u, 0.8) - np.float32(2.0)).astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------
+# aligner: TrainingInterfaces/Text_to_Spectrogram/AutoAligner/Aligner.py:37-60
+# --------------------------------------------------------------------------------------
+ALIGNER_DIM, ALIGNER_SYMBOLS = 512, 145
+
+
+def aligner_state_dict(seed: int = 3141) -> dict:
+    """Reference-schema state dict of ``Aligner`` (keys ``convs.{0,2,4,6,8}.conv/bnorm``, ``rnn.*_l0[_reverse]``, ``proj.*``).  Tamed
+    so that alignments spread over the tokens: kaiming-scaled convs, BatchNorm statistics near those of a ReLU output (positive
+    running variances), PyTorch-default LSTM ranges, and an output projection whose weights are 4x the default range while its
+    bias is a tenth of it - with the default ranges a per-symbol bias outweighs the frame-to-frame variation and one token takes
+    nearly every frame."""
+    sd = {}
+    cin = N_MEL
+    for i in range(5):
+        p = f"convs.{2 * i}."
+        sd[p + "conv.weight"] = normal("al.conv%d" % i, (ALIGNER_DIM, cin, 3), seed, std=float(np.sqrt(2.0 / (cin * 3))))
+        sd[p + "bnorm.weight"] = normal("al.bnw%d" % i, (ALIGNER_DIM,), seed, 0.1, 1.0)
+        sd[p + "bnorm.bias"] = normal("al.bnb%d" % i, (ALIGNER_DIM,), seed, 0.1)
+        sd[p + "bnorm.running_mean"] = uniform("al.bnm%d" % i, (ALIGNER_DIM,), seed, 0.2, 0.6)
+        sd[p + "bnorm.running_var"] = uniform("al.bnv%d" % i, (ALIGNER_DIM,), seed, 0.5, 1.5)
+        sd[p + "bnorm.num_batches_tracked"] = np.array(100, dtype=np.int64)
+        cin = ALIGNER_DIM
+    k = float(1.0 / np.sqrt(ALIGNER_DIM))
+    for suf in ("", "_reverse"):
+        for nm, shape in (("weight_ih", (4 * ALIGNER_DIM, ALIGNER_DIM)), ("weight_hh", (4 * ALIGNER_DIM, ALIGNER_DIM)), ("bias_ih", (4 * ALIGNER_DIM,)),
+                          ("bias_hh", (4 * ALIGNER_DIM,))):
+            sd[f"rnn.{nm}_l0{suf}"] = uniform(f"al.lstm.{nm}{suf}", shape, seed, -k, k)
+    b = float(1.0 / np.sqrt(2 * ALIGNER_DIM))
+    sd["proj.weight"] = uniform("al.proj", (ALIGNER_SYMBOLS, 2 * ALIGNER_DIM), seed, -4 * b, 4 * b)
+    sd["proj.bias"] = uniform("al.projb", (ALIGNER_SYMBOLS,), seed, -0.1 * b, 0.1 * b)
+    return sd
+
+
+def aligner_spectrogram(u: int, frames: int) -> np.ndarray:
+    """Seeded stand-in for an aligner input log-mel [frames, 80], smooth in time as speech is: a 9-frame moving average of N(0,1)
+    noise plus a little frame noise (arithmetic only, like everything here)."""
+    base = normal(f"alspec.b{u}", (frames + 8, N_MEL), 9000 + u).astype(np.float64)
+    c = np.concatenate([np.zeros((1, N_MEL)), np.cumsum(base, axis=0)])
+    smooth = (c[9:] - c[:-9]) / 3.0  # sum of 9 / 3: unit spread again
+    return (smooth + normal(f"alspec.n{u}", (frames, N_MEL), 9000 + u, 0.3) - 2.0).astype(np.float32)
+
+
+def reference_wave(u: int, n: int) -> np.ndarray:
+    """Seeded stand-in for a 16 kHz recording of n samples: N(0, 0.2) noise under an envelope that changes every 256 samples,
+    smoothed over three of them (float64, arithmetic only)."""
+    w = normal("clone.wave%d" % u, (n,), 11000 + u, 0.2).astype(np.float64)
+    env = np.convolve(uniform("clone.env%d" % u, (n // 256 + 1,), 11000 + u, 0.05, 1.0).astype(np.float64), np.ones(3) / 3, "same")
+    return w * np.repeat(env, 256)[:n]

@@ -84,6 +84,16 @@ def write_fixture_checkpoints(models_dir=MODELS_DIR, n_lang=8000):
         torch.save(obj, os.path.join(models_dir, sub, "embedding_function.pt" if sub == "Embedding" else "best.pt"))
 
 
+def write_fixture_aligner_checkpoint(models_dir=MODELS_DIR):
+    """Write the seeded fixture aligner in the reference's layout: Models/Aligner/aligner.pt = {"asr_model": state_dict}
+    (UtteranceCloner.py:33-34)."""
+    from . import fixture_weights as fw
+    os.makedirs(os.path.join(models_dir, "Aligner"), exist_ok=True)
+    path = os.path.join(models_dir, "Aligner", "aligner.pt")
+    torch.save({"asr_model": {k: torch.from_numpy(np.array(v)) for k, v in fw.aligner_state_dict().items()}}, path)
+    return path
+
+
 class ToucanTTSInterface(torch.nn.Module):
 
     def __init__(self,
