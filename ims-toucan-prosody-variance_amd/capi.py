@@ -170,6 +170,15 @@ ALIGN_PROTOTYPES = {
     "tts_token_average": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
 }
 
+# symbol -> (restype, argtypes); mirrors include/toucan_score.h (the corpus scorer: csrc/score.hip, stage entries in csrc/pipeline.hip)
+SCORE_PROTOTYPES = {
+    "tts_ctc_loss": (C.c_int, [_p, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "tts_score_losses": (C.c_int, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
+    "tts_teacher_forced": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(_i), _p]),
+    "tts_copy_decoder_mel": (C.c_int, [_p, _p, _i, _p]),
+}
+CTC_MAX_TARGETS = 2048  # include/toucan_score.h TTS_CTC_MAX_TARGETS
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -192,7 +201,7 @@ def lib():
     import torch  # noqa: F401
     handle = C.CDLL(LIB_PATH)
     _assert_single_hip_runtime()
-    for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

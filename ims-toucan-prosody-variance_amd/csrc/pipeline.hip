@@ -6,6 +6,7 @@
 //   tts_encoder               Conformer.forward (Layers/Conformer.py:92-134) on the phoneme features
 //   tts_variance_predictors   VariancePredictor.forward / DurationPredictor.inference (VariancePredictor.py:65-80, DurationPredictor.py:63-83)
 //   tts_control_and_regulate  InferenceToucanTTS.py:214-235 (+ _scale_variance :333-343, LengthRegulator.py:37-61)
+//   tts_teacher_forced        the scorer's replacement of the two above: ToucanTTS.py:321-330 (include/toucan_score.h)
 //   tts_decoder               decoder Conformer + feat_out (InferenceToucanTTS.py:238-239)
 //   tts_postnet               PostNet.forward + residual (PostNet.py:62-74, InferenceToucanTTS.py:241)
 //   tts_postflow              Glow.forward(infer=True) (Glow.py:342-391)
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "common.h"
+#include "../../include/toucan_score.h"
 
 namespace tts {
 
@@ -899,6 +901,69 @@ int pipeline_control_regulate(Handle* h, float duration_scale, float pitch_scale
                              cat + 80, 80 + ATT, dec, ATT, sqrtf((float)ATT), st);
 }
 
+// ---- stage A.2 + A.3 with teacher forcing (the scorer): raw predictions, gold prosody, gold durations -----------------------
+// ToucanTTS._forward, training branch (ToucanTTS.py:321-330): every predictor runs and its raw output is the caller's; the GOLD
+// pitch / energy are embedded and the GOLD durations expand the text.  No tts_prosody_control: no overrides, no scales.
+int pipeline_teacher_forced(Handle* h, const float* gold_pitch, const float* gold_energy, const int* gold_dur, float* pred_log_dur,
+                            float* pred_pitch, float* pred_energy, int* frames_out, hipStream_t st) {
+  TTS_CHECK_ARG(h && h->enc, "tts_teacher_forced: run tts_encoder first");
+  TTS_CHECK_ARG(gold_pitch && gold_energy && gold_dur && pred_log_dur && pred_pitch && pred_energy, "tts_teacher_forced: null pointer");
+  h->split_mode = 2;
+  h->tab_which = 0;
+  const int R = h->lp.total, B = h->B;
+  if (h->cfg.multispeaker) {
+    const Dev* w;
+    TTS_TRY(need(h, "cln_weights", &w));
+    const int n_mlp = (int)(w->bytes / 4 / tts_cln_mlp_weight_floats(64, 256));
+    TTS_ALLOC(cln, h->phone, float, (size_t)n_mlp * B * 256);
+    TTS_TRY(tts_cln_mlp(h->e_norm, B, 64, 256, static_cast<const float*>(w->p), n_mlp, cln, st));
+    h->cln = cln;
+  }
+  // conditional layer norms: pitch 0..6, energy 7..8, duration 9..11 (as in pipeline_predictors)
+  TTS_TRY(predictor(h, "pitch", 7, 0, pred_pitch, st));
+  TTS_TRY(predictor(h, "energy", 2, 7, pred_energy, st));
+  TTS_TRY(predictor(h, "duration", 3, 9, pred_log_dur, st));
+  TTS_TRY(hip_ok(hipMemcpyAsync(h->pitch, gold_pitch, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold pitch"));
+  TTS_TRY(hip_ok(hipMemcpyAsync(h->energy, gold_energy, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold energy"));
+  TTS_TRY(hip_ok(hipMemcpyAsync(h->dur, gold_dur, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold durations"));
+  std::vector<int> d_host(R);
+  TTS_TRY(hip_ok(hipMemcpyAsync(d_host.data(), gold_dur, (size_t)R * 4, hipMemcpyDeviceToHost, st), "durations to host"));
+  TTS_TRY(hip_ok(hipStreamSynchronize(st), "durations to host: sync"));
+  h->frames.assign(B, 0);
+  for (int u = 0; u < B; ++u) {
+    long long t = 0;
+    for (int i = 0; i < h->lp.lengths[u]; ++i) {
+      const int d = d_host[h->lp.begins[u] + i];
+      TTS_CHECK_ARG(d >= 0, "tts_teacher_forced: utterance %d, phoneme %d: negative gold duration %d", u, i, d);
+      t += d;
+    }
+    TTS_CHECK_ARG(t <= (1 << 24), "tts_teacher_forced: utterance %d: %lld frames", u, t);
+    h->frames[u] = t > 0 ? (int)t : h->lp.lengths[u];  // LengthRegulator.py:52-53: an all-zero utterance becomes all ones
+    if (frames_out) frames_out[u] = h->frames[u];
+  }
+  h->lf = Layout::make(h->frames.data(), B, 2);
+  const size_t RF = h->lf.total;
+  TTS_TRY(arena_reserve(h->frame, frame_arena_bytes(RF), st));
+  Arena& a = h->frame;
+  TTS_ALLOC(cat, a, float, RF * (80 + ATT));
+  TTS_TRY(hip_ok(hipMemsetAsync(cat, 0, RF * (80 + ATT) * 4, st), "clear frame buffer"));
+  TTS_ALLOC(dec, a, float, RF * ATT);
+  h->cat = cat;
+  h->dec = dec;
+  const float *wp, *bp, *we, *be;
+  TTS_TRY(fvec(h, "pitch_w", &wp));
+  TTS_TRY(fvec(h, "pitch_b", &bp));
+  TTS_TRY(fvec(h, "energy_w", &we));
+  TTS_TRY(fvec(h, "energy_b", &be));
+  const int *pb, *pe, *fb, *fe;
+  TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
+  TTS_TRY(bounds_of(h, h->lf, st, &fb, &fe));
+  // tts_length_regulate forms enc + (first * w1 + b1) + (second * w2 + b2): energy passed first gives the training order
+  // encoded + energy_embed + pitch_embed (the inference order adds pitch first)
+  return tts_length_regulate(h->enc, ATT, h->energy, h->pitch, we, be, wp, bp, h->dur, pb, pe, fb, B, h->lf.max_len, h->lp.max_len, ATT,
+                             cat + 80, 80 + ATT, dec, ATT, sqrtf((float)ATT), st);
+}
+
 // ---- stage B.1: decoder + feat_out --------------------------------------------------------------------------------------
 int pipeline_decoder(Handle* h, hipStream_t st) {
   TTS_CHECK_ARG(h && h->dec, "tts_decoder: run tts_control_and_regulate first");
@@ -1258,6 +1323,12 @@ int tts_control_and_regulate(TtsHandle* h, float duration_scale, float pitch_sca
   return tts::stage_done(H(h), 0, ST(stream),
                          tts::pipeline_control_regulate(H(h), duration_scale, pitch_scale, energy_scale, pause_scale, frame_counts, ST(stream)));
 }
+int tts_teacher_forced(TtsHandle* h, const float* gold_pitch, const float* gold_energy, const int32_t* gold_durations, float* pred_log_dur,
+                       float* pred_pitch, float* pred_energy, int32_t* frame_counts, tts_stream_t stream) {
+  return tts::stage_done(H(h), 0, ST(stream),
+                         tts::pipeline_teacher_forced(H(h), gold_pitch, gold_energy, gold_durations, pred_log_dur, pred_pitch, pred_energy,
+                                                      frame_counts, ST(stream)));
+}
 int tts_decoder(TtsHandle* h, tts_stream_t stream) { return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_decoder(H(h), ST(stream))); }
 int tts_postnet(TtsHandle* h, tts_stream_t stream) { return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_postnet(H(h), ST(stream))); }
 int tts_postflow(TtsHandle* h, const float* z_noise, tts_stream_t stream) {
@@ -1341,6 +1412,19 @@ int tts_copy_mel(TtsHandle* h, float* dst, int32_t ld_dst, tts_stream_t stream) 
   const hipError_t e = hipMemcpy2DAsync(dst, (size_t)ld_dst * 4, hh->mel, (size_t)ld * 4, 80 * 4, hh->lf.total, hipMemcpyDeviceToDevice, ST(stream));
   if (e != hipSuccess) {
     tts::set_error("tts_copy_mel: %s", hipGetErrorString(e));
+    return TTS_E_LAUNCH;
+  }
+  return TTS_OK;
+}
+int tts_copy_decoder_mel(TtsHandle* h, float* dst, int32_t ld_dst, tts_stream_t stream) {
+  tts::Handle* hh = H(h);
+  if (!hh || !hh->mel0 || !dst || ld_dst < 80) {
+    tts::set_error("tts_copy_decoder_mel: no decoder output yet / null destination / row stride %d < 80", (int)ld_dst);
+    return TTS_E_ARG;
+  }
+  const hipError_t e = hipMemcpy2DAsync(dst, (size_t)ld_dst * 4, hh->mel0, 80 * 4, 80 * 4, hh->lf.total, hipMemcpyDeviceToDevice, ST(stream));
+  if (e != hipSuccess) {
+    tts::set_error("tts_copy_decoder_mel: %s", hipGetErrorString(e));
     return TTS_E_LAUNCH;
   }
   return TTS_OK;

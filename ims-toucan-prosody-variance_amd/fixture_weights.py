@@ -397,3 +397,61 @@ def reference_wave(u: int, n: int) -> np.ndarray:
     w = normal("clone.wave%d" % u, (n,), 11000 + u, 0.2).astype(np.float64)
     env = np.convolve(uniform("clone.env%d" % u, (n // 256 + 1,), 11000 + u, 0.05, 1.0).astype(np.float64), np.ones(3) / 3, "same")
     return w * np.repeat(env, 256)[:n]
+
+
+# --------------------------------------------------------------------------------------
+# corpus caches of the scorer (Utility/Scorer.py): aligner_train_cache.pt (AlignerDataset.py:84-110) and fast_train_cache.pt
+# (FastSpeechDataset.py:97-105), written from seeded phoneme strings
+# --------------------------------------------------------------------------------------
+def fixture_phone_string(u: int, n_words: int, seed: int) -> str:
+    """Seeded phoneme string: '~', n_words words of 1 .. 6 phonemes separated by word boundaries (' '), '~#'."""
+    from .phonemes import phone_table
+    table = phone_table()
+    syms = sorted(s for s, v in table.items() if v[15] == 1 and v[21] == 0)
+    lens = 1 + (uniform01("corpus.wlen%d" % u, n_words, seed) * 6).astype(int)
+    idx = (uniform01("corpus.syms%d" % u, int(lens.sum()), seed) * len(syms)).astype(int)
+    words, k = [], 0
+    for n in lens:
+        words.append("".join(syms[i] for i in idx[k:k + n]))
+        k += n
+    return "~" + " ".join(words) + "~#"
+
+
+def write_fixture_corpus(corpus_dir: str, n: int, seed: int = 0, words=(2, 8), max_duration: int = 8) -> list:
+    """Write ``aligner_train_cache.pt`` and ``fast_train_cache.pt`` into corpus_dir in the reference's layout, for n seeded utterances:
+
+    * text: ``phones_to_features`` of ``fixture_phone_string`` ([L, 62], word boundaries included);
+    * durations [L] (int64): 0 at the word boundaries, seeded 1 .. max_duration elsewhere; the mel has exactly their sum of frames;
+    * mel [T, 80]: ``aligner_spectrogram``; pitch and energy [L, 1]: seeded in [0.3, 1.7) at EVERY token, word boundaries and unvoiced
+      phonemes included (so an override the scorer must not apply would show);
+    * the aligner cache's waves (T * 256 samples) and speaker embeddings are seeded placeholders: the scorers do not read them.
+
+    Returns the file paths (the key of the scorers' results)."""
+    import os
+    import torch
+    from .phonemes import IDX, phones_to_features
+    os.makedirs(corpus_dir, exist_ok=True)
+    aligner_points, fast_points, waves, spk, paths = [], [], [], [], []
+    for i in range(n):
+        u = 100000 * seed + i
+        nw = int(words[0] + uniform01("corpus.nw", n, seed)[i] * (words[1] - words[0] + 1))
+        feats = phones_to_features(fixture_phone_string(u, nw, seed), handle_missing=False)
+        L = feats.shape[0]
+        wb = feats[:, IDX["word_boundary"]] != 0
+        dur = (1 + (uniform01("corpus.dur%d" % u, L, seed) * max_duration).astype(np.int64))
+        dur[wb] = 0
+        T = int(dur.sum())
+        mel = aligner_spectrogram(u, T)
+        pitch = (0.3 + 1.4 * uniform01("corpus.pitch%d" % u, L, seed)).astype(np.float32).reshape(L, 1)
+        energy = (0.3 + 1.4 * uniform01("corpus.energy%d" % u, L, seed)).astype(np.float32).reshape(L, 1)
+        path = os.path.join(corpus_dir, "wav", "utt_%05d.wav" % i)
+        text, text_len = torch.from_numpy(feats), torch.LongTensor([L])
+        spec, spec_len = torch.from_numpy(mel), torch.LongTensor([T])
+        aligner_points.append([text, text_len, spec, spec_len])
+        fast_points.append([text, text_len, spec, spec_len, torch.from_numpy(dur), torch.from_numpy(energy), torch.from_numpy(pitch), None, path])
+        waves.append(torch.from_numpy(np.random.default_rng([seed, i]).normal(0.0, 0.1, T * 256).astype(np.float32)))
+        spk.append(torch.from_numpy(normal("corpus.spk%d" % u, (192,), seed).astype(np.float32)))
+        paths.append(path)
+    torch.save((aligner_points, waves, spk, paths), os.path.join(corpus_dir, "aligner_train_cache.pt"))
+    torch.save(fast_points, os.path.join(corpus_dir, "fast_train_cache.pt"))
+    return paths

@@ -1,0 +1,65 @@
+/*
+ * toucan_score.h - C ABI of the corpus scorer in libtoucan_hip.so: the reference's Utility/Scorer.py (AlignmentScorer :24-76,
+ * TTSScorer :79-199).  Same conventions as toucan_tts.h and toucan_align.h (device pointers owned by the caller, time-major packed
+ * rows, one hipStream_t per call, 0 or a negative TTS_E_* code, tts_last_error()).  The aligner's logits come from the entries of
+ * toucan_align.h and tts_conv1d; the acoustic model's forward pass from the stage API of toucan_tts.h, with tts_teacher_forced in
+ * place of tts_variance_predictors + tts_control_and_regulate.  The only caller is the build's own Python host
+ * (ims-toucan-prosody-variance_amd/scorer.py, via ctypes: capi.SCORE_PROTOTYPES).
+ *
+ * Every entry computes an utterance in an order that depends on that utterance alone: a batch returns bit for bit what its
+ * utterances return one by one (the stage entries inherit the batch behaviour of the stages they share with synthesis).
+ */
+#ifndef TOUCAN_SCORE_H
+#define TOUCAN_SCORE_H
+
+#include "toucan_tts.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- kernels (csrc/score.hip) ---- */
+
+/* CTC loss of the aligner (Aligner.py:60,107: CTCLoss(blank, zero_infinity=True), reduction "mean" at batch 1), one workgroup per
+ * utterance.  Utterance b: logits rows frame_begin[b] ... (n_frames[b] >= 1 of them, n_symbols columns, row stride ld); targets
+ * targets[target_begin[b] ...] (n_targets[b] ids in [0, n_symbols), none equal to blank).  The log-softmax of each frame is taken
+ * in the workgroup in fp32 (as the reference's fp32 log_softmax); the forward variables over the 2n+1 extended states are carried
+ * in fp64.  loss[b] = -log p(targets | logits) / max(n_targets, 1); an infeasible alignment gives 0 (zero_infinity).
+ * n_targets == 0 is handled as torch handles it: the all-blank path, divided by 1.  max_targets: the largest n_targets of the
+ * batch (0 .. TTS_CTC_MAX_TARGETS: the fp64 rows, the labels and a 32-frame block of log-probabilities live in LDS, at most
+ * 114 KiB); n_symbols <= 256. */
+#define TTS_CTC_MAX_TARGETS 2048
+int tts_ctc_loss(const float* logits, int32_t ld, int32_t n_symbols, const int32_t* frame_begin, const int32_t* n_frames,
+                 const int32_t* targets, const int32_t* target_begin, const int32_t* n_targets, int32_t batch, int32_t blank,
+                 int32_t max_targets, float* loss, tts_stream_t stream);
+
+/* The four teacher-forced losses of ToucanTTSLoss (ToucanTTSLoss.py:20-66) at batch 1, one workgroup per utterance, summed in fp64 in
+ * a fixed order (no atomics): out[b][0] l1 = (sum |before - gold| + sum |after - gold|) / (T * 80); out[b][1] duration =
+ * mean_k (log_dur[k] - log(gold_dur[k] + 1))^2 (DurationPredictorLoss, offset 1); out[b][2] pitch = mean_k (pitch[k] - gold_pitch[k])^2;
+ * out[b][3] energy likewise.  Mels: 80 channels, rows frame_begin[b] ... (n_frames[b]) of before / after / gold with their own
+ * row strides; per-phoneme vectors: phone_begin[b] ... (n_phones[b]).  The element differences are fp32, as the reference's. */
+int tts_score_losses(const float* before, int32_t ld_before, const float* after, int32_t ld_after, const float* gold, int32_t ld_gold,
+                     const int32_t* frame_begin, const int32_t* n_frames, const float* log_dur, const float* pitch, const float* energy,
+                     const int32_t* gold_dur, const float* gold_pitch, const float* gold_energy, const int32_t* phone_begin,
+                     const int32_t* n_phones, int32_t batch, float* out, tts_stream_t stream);
+
+/* ---- stage API: teacher forcing (csrc/pipeline.hip) ---- */
+
+/* After tts_encoder: the training branch of ToucanTTS._forward (ToucanTTS.py:321-330).  Runs the CLN MLP (multi-speaker) and all
+ * three predictors, writing their raw outputs into the caller's packed phoneme buffers (pred_log_dur: log domain, nothing rounded);
+ * embeds the GOLD pitch and energy in the training order (encoded + energy_embed + pitch_embed) and expands by the GOLD durations
+ * (LengthRegulator; an all-zero utterance takes one frame per phoneme).  No linguistic overrides and no scales (no
+ * tts_prosody_control).  Gold and predicted vectors: packed like the text of tts_encoder.  frame_counts (host, B): the frames
+ * per utterance.  tts_decoder and tts_postnet follow unchanged; tts_copy_prosody returns the gold values. */
+int tts_teacher_forced(TtsHandle* h, const float* gold_pitch, const float* gold_energy, const int32_t* gold_durations, float* pred_log_dur,
+                       float* pred_pitch, float* pred_energy, int32_t* frame_counts /*host*/, tts_stream_t stream);
+
+/* The decoder's mel after feat_out and before the PostNet (before_outs), [frames, 80] in the frame layout of the batch, into dst
+ * (row stride ld_dst >= 80).  Valid after tts_decoder. */
+int tts_copy_decoder_mel(TtsHandle* h, float* dst, int32_t ld_dst, tts_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* TOUCAN_SCORE_H */
