@@ -179,6 +179,23 @@ SCORE_PROTOTYPES = {
 }
 CTC_MAX_TARGETS = 2048  # include/toucan_score.h TTS_CTC_MAX_TARGETS
 
+
+class TtsGanConvDesc(C.Structure):
+    _fields_ = [
+        ("x", _p), ("w", _p), ("scale", _p), ("shift", _p), ("res", _p), ("y", _p),
+        ("n", _i), ("h", _i), ("cin", _i), ("cout", _i), ("taps", _i),
+        ("flags", _i),
+        ("pre_slope", _f), ("res_ratio", _f), ("slope", _f),
+    ]
+
+
+# symbol -> (restype, argtypes); mirrors include/toucan_gan.h (the speaker-embedding GAN: csrc/gan.hip) one to one
+GAN_PROTOTYPES = {
+    "tts_gan_conv2d": (C.c_int, [C.POINTER(TtsGanConvDesc), _p]),
+}
+GAN_KC, GAN_NC = 16, 64  # include/toucan_gan.h TTS_GAN_KC, TTS_GAN_NC: weight packing
+GAN_UPSAMPLE, GAN_PRE_LRELU, GAN_RESIDUAL, GAN_RES_UPSAMPLE, GAN_LRELU = 1, 2, 4, 8, 16  # TTS_GAN_* flags
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -201,7 +218,8 @@ def lib():
     import torch  # noqa: F401
     handle = C.CDLL(LIB_PATH)
     _assert_single_hip_runtime()
-    for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
+            list(GAN_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

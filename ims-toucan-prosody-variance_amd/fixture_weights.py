@@ -455,3 +455,72 @@ def write_fixture_corpus(corpus_dir: str, n: int, seed: int = 0, words=(2, 8), m
     torch.save((aligner_points, waves, spk, paths), os.path.join(corpus_dir, "aligner_train_cache.pt"))
     torch.save(fast_points, os.path.join(corpus_dir, "fast_train_cache.pt"))
     return paths
+
+
+# --------------------------------------------------------------------------------------
+# speaker-embedding GAN: InferenceInterfaces/Controllability/wgan/resnet_1.py (ResNet_G :8-80, ResNet_D :83-130,
+# ResNetBlock :133-181), saved by wgan_qc.py:260-275 from nn.DataParallel (keys prefixed "module.")
+# --------------------------------------------------------------------------------------
+GAN_PARAMS = dict(model="resnet", z_dim=32, size=16, nfilter=32, nfilter_max=512, data_dim=(1, 1, UTT), learning_rate=1e-4,
+                  betas=(0.5, 0.9), epochs=1, batch_size=128, n_max_iterations=1, gamma=0.1)
+
+
+def _gan_bn(sd, p, c, seed):
+    """Non-trivial eval statistics and affine terms, so that folding them is exercised."""
+    sd[p + ".weight"] = uniform(p + ".g", (c,), seed, 0.7, 1.3)
+    sd[p + ".bias"] = normal(p + ".b", (c,), seed, 0.1)
+    sd[p + ".running_mean"] = normal(p + ".rm", (c,), seed, 0.2)
+    sd[p + ".running_var"] = uniform(p + ".rv", (c,), seed, 0.4, 1.6)
+    sd[p + ".num_batches_tracked"] = np.array(1000 + c, dtype=np.int64)
+
+
+def _gan_conv(name, shape, seed, gain=1.0, bias=False):
+    fan_in = int(np.prod(shape[1:]))
+    w = normal(name, shape, seed, gain / np.sqrt(fan_in))
+    return (w, normal(name + ".bias", (shape[0],), seed, 0.05)) if bias else w
+
+
+def gan_state_dicts(params=None, seed: int = 2718):
+    """(generator_state_dict, critic_state_dict) of ResNet_G / ResNet_D for ``params`` (default GAN_PARAMS), "module."-prefixed
+    as the reference saves them.  Generator weights ~ N(0, 1/fan_in) (x1.4 on the 3x3 convs) keep the activations O(1)."""
+    from . import gan
+    params = dict(GAN_PARAMS if params is None else params)
+    z_dim, data_dim, size, nf0, blocks = gan.architecture(params)
+    nf, nf_max = int(params["nfilter"]), int(params["nfilter_max"])
+    g = {}
+    g["fc.weight"], g["fc.bias"] = _gan_conv("gan.g.fc", (nf0 * 16, z_dim), seed, 1.0, bias=True)
+    _gan_bn(g, "bn1d", nf0 * 16, seed)
+    for idx, fin, fout, _ in blocks:
+        p, fh = f"resnet.{idx}.", min(fin, fout)
+        g[p + "conv_0.weight"] = _gan_conv("gan.g." + p + "c0", (fh, fin, 3, 3), seed, 1.4)
+        _gan_bn(g, p + "bn2d_0", fh, seed)
+        g[p + "conv_1.weight"] = _gan_conv("gan.g." + p + "c1", (fout, fh, 3, 3), seed, 1.4)
+        _gan_bn(g, p + "bn2d_1", fout, seed)
+        if fin != fout:
+            g[p + "conv_s.weight"] = _gan_conv("gan.g." + p + "cs", (fout, fin, 1, 1), seed)
+            _gan_bn(g, p + "bn2d_s", fout, seed)
+    g["conv_img.weight"], g["conv_img.bias"] = _gan_conv("gan.g.img", (3, nf, 3, 3), seed, 1.4, bias=True)
+    g["fc_out.weight"], g["fc_out.bias"] = _gan_conv("gan.g.out", (data_dim, 3 * size * size), seed, 1.0, bias=True)
+    assert {k: tuple(np.shape(v)) for k, v in g.items()} == gan.expected_shapes(params)
+
+    # ResNet_D(data_dim, size, nfilter, nfilter_max): not run at inference, loaded by the reference's GanWrapper.load_model
+    nlayers = int(np.log2(size / 4))
+    d, dblocks = {}, [(0, min(nf, nf_max), min(nf, nf_max)), (1, min(nf, nf_max), min(nf * 2, nf_max))]
+    dblocks += [(2 * i + 1, min(nf * 2 ** i, nf_max), min(nf * 2 ** (i + 1), nf_max)) for i in range(1, nlayers + 1)]
+    d["fc_input.weight"], d["fc_input.bias"] = _gan_conv("gan.d.in", (3 * size * size, data_dim), seed, 1.0, bias=True)
+    d["conv_img.weight"], d["conv_img.bias"] = _gan_conv("gan.d.img", (nf, 3, 3, 3), seed, 1.0, bias=True)
+    for idx, fin, fout in dblocks:
+        p, fh = f"resnet.{idx}.", min(fin, fout)
+        d[p + "conv_0.weight"], d[p + "conv_0.bias"] = _gan_conv("gan.d." + p + "c0", (fh, fin, 3, 3), seed, 1.0, bias=True)
+        d[p + "conv_1.weight"], d[p + "conv_1.bias"] = _gan_conv("gan.d." + p + "c1", (fout, fh, 3, 3), seed, 1.0, bias=True)
+        if fin != fout:
+            d[p + "conv_s.weight"] = _gan_conv("gan.d." + p + "cs", (fout, fin, 1, 1), seed)
+    d_nf0 = min(nf_max, nf * 2 ** nlayers)
+    d["fc.weight"], d["fc.bias"] = _gan_conv("gan.d.fc", (1, d_nf0 * 16), seed, 1.0, bias=True)
+    prefix = lambda sd: {"module." + k: v for k, v in sd.items()}
+    return prefix(g), prefix(d)
+
+
+def gan_dataset_stats(data_dim: int = UTT, seed: int = 2718):
+    """(dataset_mean, dataset_std) of the checkpoint: loaded by GanWrapper, not applied (normalize = False)."""
+    return normal("gan.mean", (data_dim,), seed, 0.3), uniform("gan.std", (data_dim,), seed, 0.5, 1.5)

@@ -94,6 +94,23 @@ def write_fixture_aligner_checkpoint(models_dir=MODELS_DIR):
     return path
 
 
+def write_fixture_gan_checkpoint(models_dir=MODELS_DIR, params=None, seed=2718):
+    """Write the seeded fixture speaker-embedding GAN in the reference's layout (wgan_qc.py:260-275, read by GAN.py:32-40):
+    Models/Embedding/embedding_gan.pt = {"model_parameters", "generator_state_dict", "critic_state_dict" (both "module."-prefixed),
+    "dataset_mean", "dataset_std"}."""
+    from . import fixture_weights as fw
+    params = dict(fw.GAN_PARAMS if params is None else params)
+    params["data_dim"] = tuple(params["data_dim"])
+    gen, critic = fw.gan_state_dicts(params, seed)
+    t = lambda sd: {k: torch.from_numpy(np.array(v)) for k, v in sd.items()}
+    mean, std = fw.gan_dataset_stats(params["data_dim"][-1], seed)
+    os.makedirs(os.path.join(models_dir, "Embedding"), exist_ok=True)
+    path = os.path.join(models_dir, "Embedding", "embedding_gan.pt")
+    torch.save({"model_parameters": params, "generator_state_dict": t(gen), "critic_state_dict": t(critic),
+                "dataset_mean": torch.from_numpy(mean), "dataset_std": torch.from_numpy(std)}, path)
+    return path
+
+
 class ToucanTTSInterface(torch.nn.Module):
 
     def __init__(self,
