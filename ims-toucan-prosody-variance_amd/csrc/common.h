@@ -29,13 +29,20 @@ inline int launch_status(const char* what) {
 
 // Raise a kernel's dynamic-LDS limit to the CU's 160 KiB once per (instantiation, device): `mask` is the instantiation's
 // static bit set of devices already done.  The first (eager) launch does it, so it never lands inside a stream capture.
+// The runtime refuses a dynamic limit that does not fit beside the kernel's own __shared__ variables, so those are taken off the
+// 160 KiB.  A failure is returned AND taken out of hipGetLastError, where the next launch_status would find it.
 inline hipError_t raise_lds_limit(const void* kernel, unsigned long long& mask) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   const unsigned long long bit = 1ull << (dev & 63);
   if (mask & bit) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  int room = 160 * 1024;
+  hipFuncAttributes attr;
+  if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) room -= (int)attr.sharedSizeBytes;
+  else (void)hipGetLastError();
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, room);
   if (e == hipSuccess) mask |= bit;
+  else (void)hipGetLastError();
   return e;
 }
 

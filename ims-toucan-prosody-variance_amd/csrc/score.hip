@@ -113,7 +113,10 @@ int ctc_loss(const float* logits, int ld, int n_sym, const int* frame_begin, con
   const size_t lds = (size_t)2 * s_pad * sizeof(double) + (size_t)s_pad * sizeof(int) + (size_t)CTC_CHUNK * n_sym * sizeof(float);
   TTS_CHECK_ARG(lds <= 160 * 1024, "ctc_loss: %zu bytes of LDS requested", lds);
   static unsigned long long lds_raised = 0;
-  if (lds > 64 * 1024) (void)raise_lds_limit(reinterpret_cast<const void*>(ctc_loss_kernel), lds_raised);
+  if (lds > 64 * 1024 && raise_lds_limit(reinterpret_cast<const void*>(ctc_loss_kernel), lds_raised) != hipSuccess) {
+    set_error("ctc_loss: raising the dynamic LDS limit for %zu bytes failed", lds);
+    return TTS_E_LAUNCH;
+  }
   hipLaunchKernelGGL(ctc_loss_kernel, dim3(batch), dim3(CTC_THREADS), lds, st, logits, ld, n_sym, frame_begin, n_frames, targets, target_begin,
                      n_targets, blank, s_pad, loss);
   return launch_status("ctc_loss");
