@@ -7,13 +7,16 @@ for a ragged batch of recordings:
   (:95-131), all on the device.  The convs, the LSTM input projection (BatchNorm 5 and both LSTM biases folded in) and the
   output projection run through tts_conv1d in fp32; the rest is csrc/align.hip.
 * ``extract_prosody_batch``: reference audio -> log-mel (style.LogMel's windowed DFT, whose spectrum also gives the frame energy of
-  EnergyCalculator) -> durations -> token-averaged energy and (from a given f0 track) pitch.
+  EnergyCalculator) -> durations -> token-averaged energy and pitch.  The pitch comes from an f0 track: one the caller gives, or,
+  with ``f0="track"``, the one pitch.PitchTracker computes on the device (Praat's autocorrelation method restated, PARITY UNPINNED,
+  hence opt-in); without ``f0`` the pitch is None.
 
 fp32 throughout and no precision switch: durations are integers taken from an argmax path.  Every launch computes an utterance in
 an order that depends on that utterance alone, so a batch returns bit for bit what its utterances return one by one.
 
 Not reproduced: grapheme-to-phoneme conversion (the transcript is a phoneme string), the on-line CTC fine-tuning,
-the silero voice-activity trim (``speech_bounds`` gives the speech span instead) and Praat's pitch tracker (``f0`` gives the track).
+and the silero voice-activity trim (``speech_bounds`` gives the speech span instead).  Praat itself is not reproduced bit for bit:
+``f0="track"`` runs a restatement of its published algorithm (pitch.py).
 """
 import json
 import math
@@ -22,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from . import capi, engine, packing, style
+from . import capi, engine, packing, pitch as pitch_mod, style
 from .capi import ACT_NONE, ACT_RELU
 from .phonemes import IDX, phones_to_features
 from .ragged import Ragged
@@ -267,6 +270,23 @@ class ProsodyExtractor:
         self.ops = self.aligner.ops
         self.device = self.aligner.device
         self.logmel = style.LogMel(self.device)
+        self._tracker = None
+
+    def tracked_f0(self, waves16, f0):
+        """f0 as given to ``extract`` -> one track per utterance or None: ``"track"`` (for all, or as an entry of the list) is
+        replaced by the device tracker's f0 of that wave (pitch.PitchTracker, one batch for all that ask)."""
+        if f0 is None:
+            return None
+        f0 = [f0] * len(waves16) if isinstance(f0, str) else list(f0)
+        want = [b for b, t in enumerate(f0) if isinstance(t, str)]
+        if any(f0[b] != pitch_mod.TRACK for b in want):
+            raise ValueError(f'f0 takes arrays or "{pitch_mod.TRACK}"')
+        if want:
+            if self._tracker is None:
+                self._tracker = pitch_mod.PitchTracker(self.device)
+            for b, t in zip(want, self._tracker.track([waves16[b] for b in want])):
+                f0[b] = t
+        return f0
 
     def spectra(self, waves):
         """16 kHz waves -> (spectrum [rows, re | im] packed per utterance, Ragged of the frames inside it)."""
@@ -312,9 +332,12 @@ class ProsodyExtractor:
 
     @torch.inference_mode()
     def extract(self, feats, waves16, f0=None, mels=None):
-        """feats: [L_b, 62] per utterance; waves16: speech spans at 16 kHz.  mels: optional log-mels to align on instead of the ones
-        computed here (the golden test feeds the reference's).  -> list of (durations, pitch or None, energy) CPU tensors."""
+        """feats: [L_b, 62] per utterance; waves16: speech spans at 16 kHz.  f0: None, frame-level tracks (Hz, 0 = unvoiced), or
+        "track" - for every utterance or as an entry of the list - to compute them on the device.  mels: optional log-mels to align
+        on instead of the ones computed here (the golden test feeds the reference's).
+        -> list of (durations, pitch or None, energy) CPU tensors."""
         ops, al = self.ops, self.aligner
+        f0 = self.tracked_f0(waves16, f0)
         spec, rag = self.spectra(waves16)
         if mels is None:
             x = self.log_mel(spec, rag)
@@ -358,7 +381,8 @@ class ProsodyExtractor:
 def extract_prosody_batch(extractor, phone_strings, waves, sr, f0=None, speech_bounds=None):
     """Per utterance (durations, pitch or None, energy, start_silence, end_silence), as UtteranceCloner.extract_prosody returns them.
     waves: recordings at `sr` (a list, or one array per utterance); f0: optional frame-level tracks (Hz, 0 = unvoiced, hop 256 at
-    16 kHz); speech_bounds: optional (start, end) sample indices of the speech in the normalised 16 kHz wave - the silero trim's
+    16 kHz), or "track" (for all, or in place of an utterance's track) to compute them on the device from the speech span;
+    speech_bounds: optional (start, end) sample indices of the speech in the normalised 16 kHz wave - the silero trim's
     result - else the whole wave is speech and both silences are 0."""
     srs = sr if isinstance(sr, (list, tuple)) else [sr] * len(waves)
     feats, spans, sil = [], [], []

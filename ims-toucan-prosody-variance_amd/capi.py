@@ -196,6 +196,15 @@ GAN_PROTOTYPES = {
 GAN_KC, GAN_NC = 16, 64  # include/toucan_gan.h TTS_GAN_KC, TTS_GAN_NC: weight packing
 GAN_UPSAMPLE, GAN_PRE_LRELU, GAN_RESIDUAL, GAN_RES_UPSAMPLE, GAN_LRELU = 1, 2, 4, 8, 16  # TTS_GAN_* flags
 
+# symbol -> (restype, argtypes); mirrors include/toucan_pitch.h (the pitch tracker: csrc/pitch.hip) one to one
+PITCH_PROTOTYPES = {
+    "tts_wave_stats": (C.c_int, [_p, _p, _p, _i, _p, _p]),
+    "tts_pitch_candidates": (C.c_int, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "tts_pitch_path": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
+}
+PITCH_CANDIDATES, PITCH_LAGS, PITCH_WINDOW = 15, 600, 1198  # include/toucan_pitch.h TTS_PITCH_CANDIDATES, _LAGS, _WINDOW
+PITCH_MIN_SAMPLES, PITCH_PATH_LDS_FRAMES = 1200, 2048  # TTS_PITCH_MIN_SAMPLES, TTS_PITCH_PATH_LDS_FRAMES
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -219,7 +228,7 @@ def lib():
     handle = C.CDLL(LIB_PATH)
     _assert_single_hip_runtime()
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
-            list(GAN_PROTOTYPES.items()):
+            list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

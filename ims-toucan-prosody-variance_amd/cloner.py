@@ -4,14 +4,16 @@ methods, with the prosody extracted on the GPU (align.py) for one recording or a
 Stated deviations: the transcript is a phoneme string (no G2P offline); ``on_line_fine_tune=True`` is accepted
 with a one-time warning and not performed (the reference's five SGD steps of CTC training), so the result is that of the
 eval-mode aligner; there is no silero voice-activity trim (the silences are 0 unless ``speech_bounds`` gives the speech span);
-there is no Praat pitch tracker (pitch comes from ``f0=`` or, without it, from the acoustic model given the cloned durations).
+pitch comes from ``f0=``: a frame-level track, or ``"track"`` for the device pitch tracker (pitch.py: Praat's autocorrelation
+method restated from its publication, parity with Praat unpinned and therefore opt-in; ``track_pitch=True`` makes it the default of
+this instance); with neither, pitch is None and the acoustic model predicts it from the cloned durations.
 """
 import os
 import warnings
 
 import torch
 
-from . import align, style
+from . import align, pitch, style
 from . import interface
 from .interface import ToucanTTSInterface, write_wav
 
@@ -19,10 +21,11 @@ from .interface import ToucanTTSInterface, write_wav
 class UtteranceCloner:
     _warned_fine_tune = False
 
-    def __init__(self, model_id, device, language="en", speed_over_quality=False):
+    def __init__(self, model_id, device, language="en", speed_over_quality=False, track_pitch=False):
         self.tts = ToucanTTSInterface(device=device, tts_model_path=model_id, faster_vocoder=speed_over_quality, language=language)
         self.device = device
         self.language = language
+        self.track_pitch = track_pitch  # additive: methods called without f0= behave as f0="track"
         path = os.path.join(interface.MODELS_DIR, "Aligner", "aligner.pt")
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path}: aligner checkpoint not found (offline, write the fixture one with "
@@ -39,6 +42,8 @@ class UtteranceCloner:
     def extract_prosody_batch(self, transcripts, waves, sr, f0=None, speech_bounds=None, on_line_fine_tune=True):
         """Per utterance (durations, pitch or None, energy, start_silence, end_silence) for phoneme transcripts and recordings at `sr`."""
         self._fine_tune_notice(on_line_fine_tune)
+        if f0 is None and self.track_pitch:
+            f0 = pitch.TRACK
         return align.extract_prosody_batch(self.extractor, transcripts, waves, sr, f0=f0, speech_bounds=speech_bounds)
 
     def extract_prosody(self, transcript, ref_audio_path, lang="de", on_line_fine_tune=True, f0=None, speech_bounds=None):
@@ -46,7 +51,7 @@ class UtteranceCloner:
         the phonemizer in the reference; the transcript here is already phonemes."""
         self._fine_tune_notice(on_line_fine_tune)
         wave, sr = style.read_audio(ref_audio_path)
-        return self.extract_prosody_batch([transcript], [wave], sr, f0=None if f0 is None else [f0],
+        return self.extract_prosody_batch([transcript], [wave], sr, f0=None if f0 is None else [f0],  # [f0]: an array or "track"
                                           speech_bounds=None if speech_bounds is None else [speech_bounds], on_line_fine_tune=False)[0]
 
     def clone_utterance(self, path_to_reference_audio_for_intonation, path_to_reference_audio_for_voice, transcription_of_intonation_reference,
