@@ -46,6 +46,19 @@ inline hipError_t raise_lds_limit(const void* kernel, unsigned long long& mask) 
   return e;
 }
 
+// tts_wavenet_layer with the block's conditioning conv (1 tap, 384 -> wc_n) computed inside the layer instead of read from
+// d.cond (which is ignored): cond = g * wc[:, col0 .. col0 + 383] + bc[col0 .. col0 + 383], columns a | g, in the arithmetic of
+// tts_conv1d's 16-bit path, so the layer's output is bit-identical to the two-launch form (wavenet.hip)
+struct WavenetCond {
+  const float* g;   // [rows, 384] fp32: the squeezed speaker / utterance conditioning, same packed rows as hs
+  int ld_g;
+  const void* wc;   // packed as for tts_conv1d(compute 1 / 2): [1][48][wc_n][8]
+  int wc_n;         // 1536: four layers' columns
+  int col0;         // this layer's first column (layer index * 384)
+  const float* bc;  // bias [wc_n]
+};
+int wavenet_layer_cond(const TtsWavenetDesc& d, const WavenetCond& c, hipStream_t st);
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));

@@ -494,6 +494,8 @@ int block_of(const Handle* h, const std::string& p, Block* b) {
 // every respect but the dense products of its frame stages and vocoder (three fp16 MFMAs on split operands)
 bool is16(const Handle* h) { return h->cfg.precision == TTS_COMPUTE_BF16 || h->cfg.precision == TTS_COMPUTE_F16; }
 int bits16(const Handle* h) { return is16(h) ? 16 : 32; }
+// the PostFlow runs the stand-alone cond convs (fp32 / f32x3 handles, TOUCAN_NO_FUSED_WAVENET) and needs their output buffer
+bool postflow_cond_buffer(const Handle* h) { return !is16(h) || h->no_fused_wavenet; }
 
 // relative position tables of both stacks for positions -(pmax-1) .. pmax-1 (Attention.py:177, PositionalEncoding.py:90-130):
 // ptab[s][l][pmax - 1 + p] = linear_pos_l(pe(p)); the sinusoid table "pe" is uploaded by the host (fp32, built like the reference)
@@ -614,8 +616,10 @@ size_t conformer_bytes(size_t R) { return R * (ATT * 4 * 4 + 1536 * 4 + 3 * ATT 
 size_t phone_arena_bytes(size_t R, size_t B) {
   return conformer_bytes(R) + R * (100 + 3 * ATT + 6 * 256 + 16) * 4 + B * (64 + 2 * ATT + 24 * 256 + 8) * 4 + (1 << 16);
 }
-size_t frame_arena_bytes(size_t RF) {
-  return conformer_bytes(RF) + RF * ((80 + ATT) + 2 * ATT + 3 * 80 + 2 * 256 + ATT + 160 + 4 * ATT + ATT + 8 * ATT + 64) * 4 + (64 << 20);
+// cond_buffer: the PostFlow keeps the coupling blocks' conditioning [RS, 1536] in memory (every configuration but the 16-bit ones
+// with the fused WaveNet layer, which computes it inside the layer)
+size_t frame_arena_bytes(size_t RF, bool cond_buffer) {
+  return conformer_bytes(RF) + RF * ((80 + ATT) + 2 * ATT + 3 * 80 + 2 * 256 + ATT + 160 + 4 * ATT + ATT + (cond_buffer ? 8 * ATT : 0) + 64) * 4 + (64 << 20);
 }
 // vocoder: R packed mel rows.  Arena 1 holds the pre-conv output [R, 512] fp32 and later the stages 1 and 3, arena 0 the stages 0 and 2
 // (a stage reads its input from the other arena).  Per stage: the up-sampled tensor, the stage output and two ping-pong buffers of
@@ -747,7 +751,7 @@ int pipeline_load(Handle* h, const char* name, const void* host, const int64_t* 
 long long pipeline_workspace_bytes(const Handle* h, int B, int Lmax, int Tmax) {
   if (!h || B <= 0) return 0;
   const size_t RP = (size_t)B * Lmax, RF = (size_t)B * (Tmax + 1);  // (frame layouts start every utterance on an even row)
-  size_t total = with_growth_slack(phone_arena_bytes(RP, B)) + with_growth_slack(frame_arena_bytes(RF));
+  size_t total = with_growth_slack(phone_arena_bytes(RP, B)) + with_growth_slack(frame_arena_bytes(RF, postflow_cond_buffer(h)));
   if (h->cfg.vocoder) {
     const bool fused_mode = is16(h), big = h->cfg.vocoder == 2;
     for (int a = 0; a < 2; ++a) total += with_growth_slack(vocoder_arena_bytes(RF, a, fused_mode, big));
@@ -883,7 +887,7 @@ int pipeline_control_regulate(Handle* h, float duration_scale, float pitch_scale
   }
   h->lf = Layout::make(h->frames.data(), B, 2);  // even begins: the Glow squeeze is a pure re-view
   const size_t RF = h->lf.total;
-  TTS_TRY(arena_reserve(h->frame, frame_arena_bytes(RF), st));
+  TTS_TRY(arena_reserve(h->frame, frame_arena_bytes(RF, postflow_cond_buffer(h)), st));
   Arena& a = h->frame;
   TTS_ALLOC(cat, a, float, RF * (80 + ATT));  // [refined mel | up-sampled text] = g_proj input
   TTS_TRY(hip_ok(hipMemsetAsync(cat, 0, RF * (80 + ATT) * 4, st), "clear frame buffer"));
@@ -943,7 +947,7 @@ int pipeline_teacher_forced(Handle* h, const float* gold_pitch, const float* gol
   }
   h->lf = Layout::make(h->frames.data(), B, 2);
   const size_t RF = h->lf.total;
-  TTS_TRY(arena_reserve(h->frame, frame_arena_bytes(RF), st));
+  TTS_TRY(arena_reserve(h->frame, frame_arena_bytes(RF, postflow_cond_buffer(h)), st));
   Arena& a = h->frame;
   TTS_ALLOC(cat, a, float, RF * (80 + ATT));
   TTS_TRY(hip_ok(hipMemsetAsync(cat, 0, RF * (80 + ATT) * 4, st), "clear frame buffer"));
@@ -1037,7 +1041,7 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
   TTS_TRY(hip_ok(hipMemcpyAsync(x, z_noise, (size_t)RS * 160 * 4, hipMemcpyDeviceToDevice, st), "flow noise"));
   TTS_ALLOC(hs, a, float, (size_t)RS * 2 * ATT);  // [hidden state | skip sum]
   // 16-bit configurations: one launch per WaveNet layer (tts_wavenet_layer); the state ping-pongs between hs and hs2
-  const bool fused = is16(h) && !h->no_fused_wavenet;
+  const bool fused = !postflow_cond_buffer(h);
   float* hs2 = nullptr;
   TileTab t64;
   if (fused) {
@@ -1048,9 +1052,20 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
     }
     TTS_TRY(tiles_of(h, ls, 64, st, &t64));
   }
-  TTS_ALLOC(acts, a, char, (size_t)RS * ATT * (b16 / 8));
-  TTS_ALLOC(cond, a, float, (size_t)RS * 8 * ATT);
+  // the fused layers compute their conditioning columns themselves (wavenet_layer_cond): no acts, no cond buffer
+  char* acts = nullptr;
+  float* cond = nullptr;
+  if (!fused) {
+    acts = arena_alloc<char>(a, (size_t)RS * ATT * (b16 / 8));
+    cond = arena_alloc<float>(a, (size_t)RS * 8 * ATT);
+    if (!acts || !cond) {
+      set_error("tts_postflow: workspace exhausted");
+      return TTS_E_ARG;
+    }
+  }
   float* skip = hs + ATT;
+  double live_rows = 0;  // (stage profiler)
+  for (int n : ls.lengths) live_rows += n;
   for (int b = 17; b >= 0; --b) {
     const std::string p = "flow." + std::to_string(b) + ".", grp = "flowgrp." + std::to_string(b / 4) + ".";
     ConvW start, end, cnd;
@@ -1058,7 +1073,7 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
     TTS_TRY(conv_of(h, p + "end", &end));
     TTS_TRY(conv_of(h, p + "cond", &cnd));
     TTS_TRY(conv(h, start, T2(x, 160), T2(hs, 2 * ATT), ls, st));            // h = start(x0); the zero half clears the skip sum
-    TTS_TRY(conv(h, cnd, T2(g, 2 * ATT), T2(cond, 8 * ATT), ls, st));       // squeeze of g = re-view [RS, 384]
+    if (!fused) TTS_TRY(conv(h, cnd, T2(g, 2 * ATT), T2(cond, 8 * ATT), ls, st));  // squeeze of g = re-view [RS, 384]
     float* cur = hs;
     for (int i = 0; i < 4; ++i) {
       ConvW inl, rs;
@@ -1069,11 +1084,21 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
         TtsWavenetDesc w;
         memset(&w, 0, sizeof(w));
         w.hs_in = cur; w.ld_in = 2 * ATT; w.hs_out = nxt; w.ld_out = 2 * ATT;
-        w.cond = cond + (size_t)i * 2 * ATT; w.ld_cond = 8 * ATT;
         w.w1 = inl.w16; w.b1 = inl.bias; w.w2 = rs.w16; w.b2 = rs.bias;
         w.cout2 = rs.cout; w.compute = inl.compute16;
         w.tiles = t64.dev; w.n_tiles = t64.n; w.tile_rows = 64;
-        TTS_TRY(tts_wavenet_layer(&w, st));
+        TTS_CHECK_ARG(cnd.w16 && cnd.mode == TTS_MODE_LINEAR && cnd.compute16 == inl.compute16 && cnd.cin == 2 * ATT && cnd.cin_pad == 2 * ATT && cnd.cout == 8 * ATT &&
+                          cnd.taps == 1 && cnd.wn >= 8 * ATT,
+                      "tts_postflow: %scond is not a 16-bit 1-tap 384 -> 1536 conv", p.c_str());
+        const WavenetCond wc = {g, 2 * ATT, cnd.w16, cnd.wn, i * 2 * ATT, cnd.bias};
+        ProfRec* pr = nullptr;
+        if (h->prof_on && prof_wants(h, "wavenet_layer"))  // in-layer, conditioning and res/skip products; state in and out, g, weights
+          pr = prof_open(h, "wavenet_layer", 2.0 * live_rows * (ATT * 5 * 2 * ATT + 2 * ATT * 2 * ATT + (double)ATT * rs.cout),
+                         live_rows * 4.0 * (2 * ATT + rs.cout + 2 * ATT) + 2.0 * (5 * ATT * 2 * ATT + 2 * ATT * 2 * ATT + ATT * rs.cout),
+                         live_rows * rs.cout, st);
+        const int rc = wavenet_layer_cond(w, wc, st);
+        if (pr) (void)hipEventRecord(pr->e1, st);
+        TTS_TRY(rc);
         cur = nxt;
         continue;
       }

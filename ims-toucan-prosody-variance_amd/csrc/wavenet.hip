@@ -8,10 +8,25 @@
 // the layer reads hs_in and writes hs_out (the host ping-pongs two buffers).
 //
 // Both products run transposed (weights are the MFMA A operand, accumulator row = output channel, lane = frame), so epilogues
-// work on float4 / packed 8-byte pieces of a frame's row (see resblock.hip).  Weights stream as 32-channel slabs (24 KB) through
-// a WN_RING-deep LDS ring filled by direct global->LDS loads (global_load_lds_dwordx4): no staging registers, WN_RING - 1 slabs in flight
-// across the raw s_barrier of a step, counted s_waitcnt vmcnt (cdna_hip_programming.md, "Pipelining across barriers" - this
-// kernel runs at one workgroup per CU and one wavefront per SIMD, the regime where that matters).
+// work on float4 / packed 8-byte pieces of a frame's row (see resblock.hip).
+//
+// No wavefront waits for another inside a product.  Every wavefront streams the weight columns it consumes itself straight from
+// global memory (L2) into registers as A fragments - the packed layout [tap][k/8][n][8] makes a fragment one coalesced
+// global_load_dwordx4 - WN_DEPTH k-steps ahead with counted s_waitcnt vmcnt, as gemm_rows_kernel in conv1d.hip does; only the
+// hidden-state window, and later acts, are shared in LDS.  Three barriers per layer: the window is staged; every wave is done
+// with it; acts are complete.  (The predecessor streamed 24 KB weight slabs through an LDS ring shared by the four wavefronts,
+// one barrier per slab: 36 dependent steps of ~0.9 us, neither the loads nor the MFMAs but that chain set its 32 us.)
+// Ownership: the gated conv is 12 work items (pair-block of 32 a + 32 g channels, frame block of 32), three per wavefront - one
+// pair-block over both frame blocks (each fragment feeds two MFMAs) and half of a pair-block shared with the neighbouring
+// wavefront: 4 fragments and 6 MFMAs per k-step, L2 -> CU weight traffic 8/6 of the matrix.  The res/skip conv gives a wavefront
+// three output-channel blocks over both frame blocks (last layer: the gated conv's pattern on its six blocks).
+// Accumulation order of both products is the predecessor's: tap-major, k ascending in 16-channel steps.
+//
+// Fused conditioning (wavenet_layer_cond, the PostFlow of the stage API): the block's cond conv (1 tap, 384 -> 1536) used to
+// write [rows, 1536] fp32 that the four layers read back in 384-column slices - 2.3 GB of HBM traffic per pass for a value used
+// once.  Here the layer computes its own 384 columns as a third product in the same stream, from a 16-bit LDS tile of the
+// squeezed g, into accumulators of its own and in the arithmetic of tts_conv1d's 16-bit loop (32x32x16, k ascending,
+// (acc + bias) in fp32), so the result is bit-identical to the two-launch form that engine.py keeps.
 #include "common.h"
 
 namespace tts {
@@ -21,56 +36,92 @@ constexpr int WN_H = 192;            // hidden channels
 constexpr int WN_BM = 64;            // frames per workgroup
 constexpr int WN_TAPS = 5;
 constexpr int WN_XP = WN_H + 8;      // LDS pitch of the window / of acts (16-bit elements)
-constexpr int WN_KS = 32;            // channels per weight slab
-constexpr int WN_SLAB_BYTES = (WN_KS / 8) * 384 * 16;  // 24 KB: [4][384][8] 16-bit
-constexpr int WN_SLABS1 = WN_TAPS * (WN_H / WN_KS);    // 30 slab steps of the gated conv
-constexpr int WN_SLABS2 = WN_H / WN_KS;                // 6 of the res/skip conv
-// LDS ring slots: WN_RING - 1 slabs in flight (five slots = 120 KB of the CU's 160: a global -> LDS load lands ~1.1 us after it is
-// issued, a slab step takes ~0.9 us)
-constexpr int WN_RING = 5;
-constexpr int WN_LOADS = 6;                            // global_load_lds instructions per wavefront and slab (narrow slabs re-request units)
+constexpr int WN_G = 2 * WN_H;       // channels of the squeezed g (fused conditioning)
+constexpr int WN_GP = WN_G + 8;      // LDS pitch of the g tile
+constexpr int WN_STEPS1 = WN_TAPS * (WN_H / 16);  // 60 k-steps of the gated conv
+constexpr int WN_STEPSC = WN_G / 16;              // 24 of the conditioning conv
+constexpr int WN_STEPS2 = WN_H / 16;              // 12 of the res/skip conv
+constexpr int WN_DEPTH = 4;          // k-steps of weight fragments in flight per wavefront (divides 12; six spill the fused form)
+constexpr int WN_L = 4;              // loads per wavefront and k-step, in every product (the res/skip one pads with a repeat)
+constexpr size_t WN_XS_BYTES = ((size_t)(WN_BM + WN_TAPS - 1) * WN_XP * 2 + 255) / 256 * 256;
+constexpr size_t WN_GS_BYTES = (size_t)WN_BM * WN_GP * 2;
+static_assert(WN_STEPS1 % WN_DEPTH == 0 && WN_STEPSC % WN_DEPTH == 0 && WN_STEPS2 % WN_DEPTH == 0 && (WN_H / 16) % WN_DEPTH == 0,
+              "a block of WN_DEPTH k-steps stays inside one tap and one product");
 }  // namespace
 
-template <bool F16>
-__global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc d) {
+template <bool F16, bool FUSED>
+__global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc d, const WavenetCond cd) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  unsigned short* xs = reinterpret_cast<unsigned short*>(lds_raw);                       // [68][XP] window of h, later [64][XP] acts
-  unsigned char* ring = lds_raw + ((WN_BM + WN_TAPS - 1) * WN_XP * 2 + 255) / 256 * 256;  // [WN_RING][24 KB]
+  unsigned short* xs = reinterpret_cast<unsigned short*>(lds_raw);                // [68][XP] window of h, later [64][XP] acts
+  unsigned short* gs = reinterpret_cast<unsigned short*>(lds_raw + WN_XS_BYTES);  // FUSED: [64][GP] squeezed g, 16-bit
   const TtsTile tile = d.tiles[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, lrow = lane & 31, lk = lane >> 5;
-  const int n2 = d.cout2;                       // 384 or 192
-  const int units2 = (WN_KS / 8) * n2;          // 16-byte units of a res/skip slab
-  const int total = WN_SLABS1 + WN_SLABS2;
-  const char* w1 = reinterpret_cast<const char*>(d.w1);
-  const char* w2 = reinterpret_cast<const char*>(d.w2);
+  const int tid = threadIdx.x, lane = tid & 63, lrow = lane & 31, lk = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // ownership: pair-block P0 (32 a + 32 g channels) over both frame blocks, pair-block P1 over frame block fP only
+  const int P0 = (wave * 5 + 1) / 3, P1 = wave < 2 ? 1 : 4, fP = wave & 1, fQ = fP ^ 1;  // P0 = 0, 2, 3, 5
+  const int n2 = d.cout2;  // 384 or 192
+  // res/skip: output-channel blocks 3 wave .. 3 wave + 2 over both frame blocks; the last layer (six blocks): P0 over both, P1 over fP
+  const int cb0 = n2 == 384 ? 3 * wave : P0, cb1 = n2 == 384 ? 3 * wave + 1 : P1, cb2 = n2 == 384 ? 3 * wave + 2 : P1;
 
-  // direct global -> LDS copy of weight slab s into ring[s % WN_RING]: wave w moves units i*256 + w*64 + lane (1 KB per instruction).
-  // Every slab is WN_LOADS instructions per wavefront (a narrow res/skip slab re-requests its last units), so the number of loads
-  // in flight behind a slab is a compile-time constant.  One piece = one instruction per wavefront; a step spreads the pieces of
-  // the slab it requests between its matrix instructions (issued in a block in front of them, each piece held the wavefront's
-  // issue for 100+ cycles - MI355X_MICROARCH.md, "LDS-DMA piece issue cost": 38.2 -> 34.9 us per layer)
-  auto issue_piece = [&](int s, int i) __attribute__((always_inline)) {
-    if (s >= total) return;
-    const bool second = s >= WN_SLABS1;
-    const int units = second ? units2 : (WN_KS / 8) * 384;
-    const char* src = second ? w2 + (size_t)(s - WN_SLABS1) * units2 * 16 : w1 + (size_t)s * WN_SLAB_BYTES;  // slabs are contiguous: [tap][k/8][n][8]
-    unsigned char* dst = ring + (size_t)(s % WN_RING) * WN_SLAB_BYTES;
-#ifdef WN_DIAG_NO_DMA  // (timing diagnostics only: no weight traffic, results are wrong)
-    if (s >= WN_RING) return;
-#endif
-    const int u0 = i * 256 + wave * 64;
-    int u = u0 + lane;
-    u = u < units ? u : units - 1;
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)u * 16),
-                                     (void __attribute__((address_space(3)))*)(dst + (size_t)u0 * 16), 16, 0, 0);
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#define WN_GLOAD128(dst_, ptr_) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst_) : "v"(ptr_) : "memory")
+#define WN_WAIT_VM(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
+#define WN_PIN(r_) asm volatile("" : "+v"(r_))
+  // The weight stream (see gemm_rows_kernel in conv1d.hip for the idiom): inline-asm loads the compiler does not count, WN_DEPTH
+  // k-steps ahead; they return in order, so before a k-step is consumed (WN_DEPTH - 1) * WN_L younger loads may stay in flight.
+  // One stream runs through all products: the last block of a product requests the first k-steps of the next one.
+  u32x4 wr[WN_DEPTH][WN_L];
+  const char *q0, *q1, *q2, *q3;  // this lane's four fragment addresses of the next k-step to request
+  size_t qs;                      // bytes per k-step
+  auto request = [&](int slot) __attribute__((always_inline)) {
+    WN_GLOAD128(wr[slot][0], q0);
+    WN_GLOAD128(wr[slot][1], q1);
+    WN_GLOAD128(wr[slot][2], q2);
+    WN_GLOAD128(wr[slot][3], q3);
+    q0 += qs; q1 += qs; q2 += qs; q3 += qs;
   };
-  auto issue = [&](int s) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < WN_LOADS; ++i) issue_piece(s, i);
+  auto arrive = [&](int slot) __attribute__((always_inline)) {
+    WN_WAIT_VM((WN_DEPTH - 1) * WN_L);
+    WN_PIN(wr[slot][0]);
+    WN_PIN(wr[slot][1]);
+    WN_PIN(wr[slot][2]);
+    WN_PIN(wr[slot][3]);
+  };
+  // packed [tap][k/8][n][8]: the A fragment of k-step s, column block cb = 16 bytes at ((2 s + lk) n + 32 cb + lrow) * 16
+  auto stream_pairs = [&](const void* w, int n, int col0) __attribute__((always_inline)) {  // columns a | g of P0 and of P1
+    const char* b = reinterpret_cast<const char*>(w) + ((size_t)lk * n + col0 + lrow) * 16;
+    q0 = b + P0 * 512; q1 = q0 + WN_H * 16; q2 = b + P1 * 512; q3 = q2 + WN_H * 16;
+    qs = (size_t)n * 32;
+  };
+  auto stream_res_skip = [&]() __attribute__((always_inline)) {
+    const char* b = reinterpret_cast<const char*>(d.w2) + ((size_t)lk * n2 + lrow) * 16;
+    q0 = b + cb0 * 512; q1 = b + cb1 * 512; q2 = b + cb2 * 512; q3 = q2;
+    qs = (size_t)n2 * 32;
+  };
+  auto publish = [&]() __attribute__((always_inline)) {  // this wave's LDS stores are done, then the barrier (raw: no vmcnt drain)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
   };
 
+  // ---- FUSED: this thread's share of the tile's g rows (rows past the utterance read its last row: their results are never
+  // stored).  Requested first and parked in accumulator registers until the gated conv's loop is over: the loads return in order,
+  // so the waits of the window staging below cover them and no wait of the weight stream ever meets them in flight.
+  constexpr int GQ4 = WN_G / 4, GPER = WN_BM * GQ4 / 256;  // 24 float4 per thread
+  f32x4 gv[FUSED ? GPER : 1];
+  if constexpr (FUSED) {
 #pragma unroll
-  for (int i = 0; i < WN_RING - 1; ++i) issue(i);  // the first slabs land while the window is staged (total = 36 >= WN_RING - 1)
+    for (int p = 0; p < GPER; ++p) {
+      const int e = tid + p * 256, r = e / GQ4, c4 = (e % GQ4) * 4;
+      int gr = tile.row0 + r;
+      gr = gr < tile.seq_end ? gr : tile.seq_end - 1;
+      const float* gp = cd.g + (size_t)gr * cd.ld_g + c4;
+      asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(gv[p]) : "v"(gp) : "memory");
+    }
+  }
+  stream_pairs(d.w1, 2 * WN_H, 0);
+#pragma unroll
+  for (int u = 0; u < WN_DEPTH; ++u) request(u);  // the first fragments land while the window is staged
+
   // ---- window of the hidden state: rows row0 - 2 .. row0 + 65 (zero outside the utterance = the conv's zero padding) -> 16-bit
   {
     // PER independent 16-byte loads per thread are in flight before the first is consumed (clamped addresses, no branches): one
@@ -98,167 +149,233 @@ __global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc
       }
     }
   }
-  f32x16 acc[6];
+  publish();  // (1) the window is staged
+
+  f32x16 acc[6], accc[FUSED ? 6 : 1];
 #pragma unroll
   for (int j = 0; j < 6; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
 
-  // slab s has landed; the loads of the slabs behind it (min(WN_RING - 2, slabs left) x WN_LOADS) may stay in flight
-  auto wait_for = [&](int s) __attribute__((always_inline)) {
-    const int behind = total - 1 - s;  // slabs requested behind s so far: min(behind, WN_RING - 2)
-    static_assert(WN_RING >= 3 && WN_RING <= 6, "one wait per number of slabs in flight below");
-    if (WN_RING >= 6 && behind >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * WN_LOADS) : "memory");
-    else if (WN_RING >= 5 && behind >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * WN_LOADS) : "memory");
-    else if (WN_RING >= 4 && behind >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * WN_LOADS) : "memory");
-    else if (behind >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WN_LOADS) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS stores (window / acts) are done before the barrier publishes them
-    __builtin_amdgcn_s_barrier();
+  // one k-step of a pair product: a[0..3] = P0's a (fP, fQ) and g (fP, fQ), a[4..5] = P1's a and g (fP).  xP / xQ hold this
+  // k-step's frame fragments; the next k-step's (at xnext) are read before the MFMAs, so their LDS round trip hides under them
+  auto xload = [&](bf16x8& xP, bf16x8& xQ, const unsigned short* xrow, int pitch) __attribute__((always_inline)) {
+    xP = *reinterpret_cast<const bf16x8*>(xrow + (fP * 32 + lrow) * pitch + lk * 8);
+    xQ = *reinterpret_cast<const bf16x8*>(xrow + (fQ * 32 + lrow) * pitch + lk * 8);
+  };
+  auto pair_step = [&](int slot, f32x16 (&a)[6], bf16x8& xP, bf16x8& xQ, const unsigned short* xnext, int pitch) __attribute__((always_inline)) {
+    const bf16x8 cP = xP, cQ = xQ;
+    xload(xP, xQ, xnext, pitch);
+    arrive(slot);
+    u32x4 wf[WN_L];
+#pragma unroll
+    for (int i = 0; i < WN_L; ++i) wf[i] = wr[slot][i];  // copies: the slot is re-requested below while the MFMAs may still read
+    a[0] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[0]), cP, a[0]);
+    a[1] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[0]), cQ, a[1]);
+    a[2] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[1]), cP, a[2]);
+    a[3] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[1]), cQ, a[3]);
+    a[4] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[2]), cP, a[4]);
+    a[5] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[3]), cP, a[5]);
+    request(slot);
+  };
+  bf16x8 xP, xQ;
+  auto window_at = [&](int s) __attribute__((always_inline)) {  // k-step s of the gated conv: tap s / 12, channels 16 (s % 12) ..
+    s = s < WN_STEPS1 ? s : WN_STEPS1 - 1;
+    return xs + (s / (WN_H / 16)) * WN_XP + (s % (WN_H / 16)) * 16;
   };
 
-  // ---- gated conv: acc[0..2] = a, acc[3..5] = g for channels wn*96 + j*32 ..; frames wm*32 ..
-  for (int s = 0; s < WN_SLABS1; ++s) {
-    wait_for(s);
-    const int tap = s / (WN_H / WN_KS), k0 = (s % (WN_H / WN_KS)) * WN_KS;
-    const unsigned short* wb = reinterpret_cast<const unsigned short*>(ring + (size_t)(s % WN_RING) * WN_SLAB_BYTES);
-    // all fragments of the step first (14 LDS reads in flight), then the 12 MFMAs: with one wavefront per SIMD nothing else hides
-    // an LDS round trip in front of every MFMA, which is what the compiler's own interleaving produced
-    bf16x8 xf[WN_KS / 16], wf[WN_KS / 16][6];
+  // ---- gated conv: tap-major, k ascending in 16-channel steps
+  xload(xP, xQ, window_at(0), WN_XP);
+#pragma unroll 1
+  for (int base = 0; base < WN_STEPS1; base += WN_DEPTH) {
+    if (base == WN_STEPS1 - WN_DEPTH) {  // the requests of this block are the first k-steps of the next product
+      if constexpr (FUSED) stream_pairs(cd.wc, cd.wc_n, cd.col0);
+      else stream_res_skip();
+    }
 #pragma unroll
-    for (int kk = 0; kk < WN_KS / 16; ++kk) {
-      xf[kk] = *reinterpret_cast<const bf16x8*>(xs + (wm * 32 + lrow + tap) * WN_XP + k0 + kk * 16 + lk * 8);
+    for (int u = 0; u < WN_DEPTH; ++u) pair_step(u, acc, xP, xQ, window_at(base + u + 1), WN_XP);
+  }
+  // ---- FUSED: cond = cond_conv(g)[this layer's 384 columns] into its own accumulators (1 tap, K = 384, k ascending: the
+  // arithmetic of the stand-alone conv, so acts are bit-identical to the two-launch form)
+  if constexpr (FUSED) {
 #pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const int col = (j < 3 ? 0 : WN_H) + wn * 96 + (j % 3) * 32 + lrow;
-        wf[kk][j] = *reinterpret_cast<const bf16x8*>(wb + ((size_t)(kk * 2 + lk) * 384 + col) * 8);
+    for (int p = 0; p < GPER; ++p) {
+      asm volatile("" : "+a"(gv[p]));  // (landed: older than every weight fragment consumed so far; no use moves above this)
+      const int e = tid + p * 256, r = e / GQ4, c4 = (e % GQ4) * 4;
+      *reinterpret_cast<uint2*>(gs + r * WN_GP + c4) = make_uint2(pack16<F16>(gv[p][0], gv[p][1]), pack16<F16>(gv[p][2], gv[p][3]));
+    }
+  }
+  publish();  // (2) every wave is done reading the window (and g is staged)
+  if constexpr (FUSED) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accc[j][r] = 0.0f;
+    xload(xP, xQ, gs, WN_GP);
+#pragma unroll 1
+    for (int base = 0; base < WN_STEPSC; base += WN_DEPTH) {
+      if (base == WN_STEPSC - WN_DEPTH) stream_res_skip();
+#pragma unroll
+      for (int u = 0; u < WN_DEPTH; ++u) {
+        const int s1 = base + u + 1 < WN_STEPSC ? base + u + 1 : WN_STEPSC - 1;
+        pair_step(u, accc, xP, xQ, gs + s1 * 16, WN_GP);
       }
     }
-    __builtin_amdgcn_sched_barrier(0);
-#ifndef WN_DIAG_NO_MFMA
-#pragma unroll
-    for (int kk = 0; kk < WN_KS / 16; ++kk)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        if ((kk * 6 + j) % 2 == 0) {  // one piece of the slab WN_RING - 1 steps ahead per two matrix instructions
-          issue_piece(s + WN_RING - 1, (kk * 6 + j) / 2);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        acc[j] = mfma16<F16>(wf[kk][j], xf[kk], acc[j]);
-      }
-#else
-    issue(s + WN_RING - 1);
-    for (int j = 0; j < 6; ++j) acc[j][0] += bf16_to_f32(wf[0][j][0]) + bf16_to_f32(xf[1][1]) + bf16_to_f32(wf[1][j][2]);
-#endif
-    __builtin_amdgcn_sched_barrier(0);
   }
   // ---- acts = tanh(a + bias + cond) * sigmoid(g + bias + cond) -> LDS (over the window), 16-bit
-  __builtin_amdgcn_s_barrier();  // every wave is done reading the window
   {
-    const int t = wm * 32 + lrow, row = tile.row0 + t;
-    const bool live = row < tile.seq_end;
-    const float* cr = d.cond + (size_t)(live ? row : tile.seq_end - 1) * d.ld_cond;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    auto gate = [&](const f32x16& aa, const f32x16& ag, const f32x16& ca, const f32x16& cg, int pb, int f) __attribute__((always_inline)) {
+      const int t = f * 32 + lrow, row = tile.row0 + t;
+      const float* cr = FUSED ? nullptr : d.cond + (size_t)(row < tile.seq_end ? row : tile.seq_end - 1) * d.ld_cond;
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq) {
-        const int c = wn * 96 + j * 32 + 8 * rq + 4 * lk;
+        const int c = pb * 32 + 8 * rq + 4 * lk;
         const float4 ba = *reinterpret_cast<const float4*>(d.b1 + c), bg = *reinterpret_cast<const float4*>(d.b1 + WN_H + c);
-        const float4 ca = *reinterpret_cast<const float4*>(cr + c), cg = *reinterpret_cast<const float4*>(cr + WN_H + c);
-        const float av[4] = {acc[j][4 * rq] + ba.x + ca.x, acc[j][4 * rq + 1] + ba.y + ca.y, acc[j][4 * rq + 2] + ba.z + ca.z, acc[j][4 * rq + 3] + ba.w + ca.w};
-        const float gv[4] = {acc[j + 3][4 * rq] + bg.x + cg.x, acc[j + 3][4 * rq + 1] + bg.y + cg.y, acc[j + 3][4 * rq + 2] + bg.z + cg.z,
-                             acc[j + 3][4 * rq + 3] + bg.w + cg.w};
+        float pa[4], pg[4];
+        if constexpr (FUSED) {
+          const float4 ea = *reinterpret_cast<const float4*>(cd.bc + cd.col0 + c), eg = *reinterpret_cast<const float4*>(cd.bc + cd.col0 + WN_H + c);
+          const float eav[4] = {ea.x, ea.y, ea.z, ea.w}, egv[4] = {eg.x, eg.y, eg.z, eg.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {  // what the stand-alone conv's epilogue stores: (acc + bias + 0) * 1
+            pa[q] = (ca[4 * rq + q] + eav[q]) + 0.0f;
+            pg[q] = (cg[4 * rq + q] + egv[q]) + 0.0f;
+          }
+        } else {
+          const float4 ea = *reinterpret_cast<const float4*>(cr + c), eg = *reinterpret_cast<const float4*>(cr + WN_H + c);
+          pa[0] = ea.x; pa[1] = ea.y; pa[2] = ea.z; pa[3] = ea.w;
+          pg[0] = eg.x; pg[1] = eg.y; pg[2] = eg.z; pg[3] = eg.w;
+        }
+        const float bav[4] = {ba.x, ba.y, ba.z, ba.w}, bgv[4] = {bg.x, bg.y, bg.z, bg.w};
         float v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
+          const float av = aa[4 * rq + q] + bav[q] + pa[q], gvv = ag[4 * rq + q] + bgv[q] + pg[q];
           // hardware exp / reciprocal (a few ulp, far below the 16-bit rounding of acts): with one wavefront per SIMD the
           // library tanhf / expf / IEEE division of 48 elements per lane were 6 us of a 37 us launch
-          const float th = 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * av[q])) - 1.0f;
-          v[q] = th * __builtin_amdgcn_rcpf(1.0f + __expf(-gv[q]));
+          const float th = 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * av)) - 1.0f;
+          v[q] = th * __builtin_amdgcn_rcpf(1.0f + __expf(-gvv));
         }
         *reinterpret_cast<uint2*>(xs + t * WN_XP + c) = make_uint2(pack16<F16>(v[0], v[1]), pack16<F16>(v[2], v[3]));
       }
-    }
+    };
+    constexpr int CZ = FUSED ? 1 : 0;  // (not FUSED: accc is one unused register block)
+    gate(acc[0], acc[2], accc[0 * CZ], accc[2 * CZ], P0, fP);
+    gate(acc[1], acc[3], accc[1 * CZ], accc[3 * CZ], P0, fQ);
+    gate(acc[4], acc[5], accc[4 * CZ], accc[5 * CZ], P1, fP);
 #pragma unroll
     for (int j = 0; j < 6; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
   }
-  // ---- res / skip conv: output channels wn * (n2 / 2) + j * 32 .., j < n2 / 64
-  const int half2 = n2 >> 1, nj = n2 >> 6;
-  for (int s = WN_SLABS1; s < total; ++s) {
-    wait_for(s);  // (also publishes acts on the first step)
-    const int k0 = (s - WN_SLABS1) * WN_KS;
-    const unsigned short* wb = reinterpret_cast<const unsigned short*>(ring + (size_t)(s % WN_RING) * WN_SLAB_BYTES);
-    bf16x8 xf[WN_KS / 16], wf[WN_KS / 16][6];
-#pragma unroll
-    for (int kk = 0; kk < WN_KS / 16; ++kk) {
-      xf[kk] = *reinterpret_cast<const bf16x8*>(xs + (wm * 32 + lrow) * WN_XP + k0 + kk * 16 + lk * 8);
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const int col = wn * half2 + (j < nj ? j : 0) * 32 + lrow;  // (j >= nj: a duplicate read, its MFMA is skipped)
-        wf[kk][j] = *reinterpret_cast<const bf16x8*>(wb + ((size_t)(kk * 2 + lk) * n2 + col) * 8);
-      }
+  publish();  // (3) acts are complete
+  // ---- res / skip conv: acc[2 i] = block cb_i over fP, acc[2 i + 1] over fQ (last layer: acc[0..2] only)
+  xload(xP, xQ, xs, WN_XP);
+#pragma unroll 1
+  for (int base = 0; base < WN_STEPS2; base += WN_DEPTH) {
+    if (base == WN_STEPS2 - WN_DEPTH) {  // nothing follows: the tail re-requests the last k-step (unused), no branch in the stream
+      q0 -= qs; q1 -= qs; q2 -= qs; q3 -= qs;
+      qs = 0;
     }
-    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int kk = 0; kk < WN_KS / 16; ++kk)
+    for (int u = 0; u < WN_DEPTH; ++u) {
+      const bf16x8 cP = xP, cQ = xQ;
+      const int s1 = base + u + 1 < WN_STEPS2 ? base + u + 1 : WN_STEPS2 - 1;
+      xload(xP, xQ, xs + s1 * 16, WN_XP);
+      arrive(u);
+      u32x4 wf[3];
 #pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        if ((kk * 6 + j) % 2 == 0) {
-          issue_piece(s + WN_RING - 1, (kk * 6 + j) / 2);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (j < nj) acc[j] = mfma16<F16>(wf[kk][j], xf[kk], acc[j]);
+      for (int i = 0; i < 3; ++i) wf[i] = wr[u][i];
+      acc[0] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[0]), cP, acc[0]);
+      acc[1] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[0]), cQ, acc[1]);
+      acc[2] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[1]), cP, acc[2]);
+      if (n2 == 384) {
+        acc[3] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[1]), cQ, acc[3]);
+        acc[4] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[2]), cP, acc[4]);
+        acc[5] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[2]), cQ, acc[5]);
       }
-    __builtin_amdgcn_sched_barrier(0);
+      request(u);
+    }
+  }
+  WN_WAIT_VM(0);  // drain the tail requests: their destination registers stay allocated (pinned) until here
+#pragma unroll
+  for (int u = 0; u < WN_DEPTH; ++u) {
+    WN_PIN(wr[u][0]);
+    WN_PIN(wr[u][1]);
+    WN_PIN(wr[u][2]);
+    WN_PIN(wr[u][3]);
   }
   // ---- [h | skip] out = in + res_skip + bias (last layer: the skip half only)
   {
-    const int row = tile.row0 + wm * 32 + lrow;
-    if (row < tile.seq_end) {
-      const int col0 = n2 == 384 ? 0 : WN_H;
+    const int col0 = n2 == 384 ? 0 : WN_H;
+    auto store_block = [&](const f32x16& a, int cb, int f) __attribute__((always_inline)) {
+      const int row = tile.row0 + f * 32 + lrow;
+      if (row >= tile.seq_end) return;
       const float* ir = d.hs_in + (size_t)row * d.ld_in + col0;
       float* orow = d.hs_out + (size_t)row * d.ld_out + col0;
 #pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        if (j < nj) {
-#pragma unroll
-          for (int rq = 0; rq < 4; ++rq) {
-            const int c = wn * half2 + j * 32 + 8 * rq + 4 * lk;
-            const float4 b = *reinterpret_cast<const float4*>(d.b2 + c), x = *reinterpret_cast<const float4*>(ir + c);
-            *reinterpret_cast<float4*>(orow + c) = make_float4((acc[j][4 * rq] + b.x) + x.x, (acc[j][4 * rq + 1] + b.y) + x.y,
-                                                               (acc[j][4 * rq + 2] + b.z) + x.z, (acc[j][4 * rq + 3] + b.w) + x.w);
-          }
-        }
+      for (int rq = 0; rq < 4; ++rq) {
+        const int c = cb * 32 + 8 * rq + 4 * lk;
+        const float4 b = *reinterpret_cast<const float4*>(d.b2 + c), x = *reinterpret_cast<const float4*>(ir + c);
+        *reinterpret_cast<float4*>(orow + c) = make_float4((a[4 * rq] + b.x) + x.x, (a[4 * rq + 1] + b.y) + x.y, (a[4 * rq + 2] + b.z) + x.z, (a[4 * rq + 3] + b.w) + x.w);
       }
+    };
+    store_block(acc[0], cb0, fP);
+    store_block(acc[1], cb0, fQ);
+    store_block(acc[2], cb1, fP);
+    if (n2 == 384) {
+      store_block(acc[3], cb1, fQ);
+      store_block(acc[4], cb2, fP);
+      store_block(acc[5], cb2, fQ);
     }
   }
+#undef WN_GLOAD128
+#undef WN_WAIT_VM
+#undef WN_PIN
 }
 
-int wavenet_layer(const TtsWavenetDesc& d, hipStream_t st) {
-  TTS_CHECK_ARG(d.hs_in && d.hs_out && d.cond && d.w1 && d.b1 && d.w2 && d.b2 && d.tiles, "wavenet_layer: null pointer");
+namespace {
+int wavenet_launch(const TtsWavenetDesc& d, const WavenetCond* c, hipStream_t st) {
+  TTS_CHECK_ARG(d.hs_in && d.hs_out && d.w1 && d.b1 && d.w2 && d.b2 && d.tiles, "wavenet_layer: null pointer");
   TTS_CHECK_ARG(d.hs_in != d.hs_out, "wavenet_layer: the hidden state cannot be updated in place (the 5-tap conv reads neighbouring tiles)");
   TTS_CHECK_ARG(d.cout2 == 384 || d.cout2 == 192, "wavenet_layer: res/skip width %d (384, or 192 for the last layer)", d.cout2);
   TTS_CHECK_ARG(d.compute == TTS_COMPUTE_BF16 || d.compute == TTS_COMPUTE_F16, "wavenet_layer: 16-bit MFMA configurations only (compute %d)", d.compute);
   TTS_CHECK_ARG(d.tile_rows == WN_BM, "wavenet_layer: tile table must use %d rows, got %d", WN_BM, d.tile_rows);
-  TTS_CHECK_ARG((d.ld_in & 3) == 0 && (d.ld_out & 3) == 0 && (d.ld_cond & 3) == 0 && ((uintptr_t)d.hs_in & 15) == 0 && ((uintptr_t)d.hs_out & 15) == 0 &&
-                    ((uintptr_t)d.cond & 15) == 0 && ((uintptr_t)d.w1 & 15) == 0 && ((uintptr_t)d.w2 & 15) == 0 && ((uintptr_t)d.b1 & 15) == 0 &&
-                    ((uintptr_t)d.b2 & 15) == 0,
+  TTS_CHECK_ARG((d.ld_in & 3) == 0 && (d.ld_out & 3) == 0 && ((uintptr_t)d.hs_in & 15) == 0 && ((uintptr_t)d.hs_out & 15) == 0 && ((uintptr_t)d.w1 & 15) == 0 &&
+                    ((uintptr_t)d.w2 & 15) == 0 && ((uintptr_t)d.b1 & 15) == 0 && ((uintptr_t)d.b2 & 15) == 0,
                 "wavenet_layer: rows and weights must be 16-byte aligned");
-  if (d.n_tiles == 0) return TTS_OK;
-  const size_t lds = ((size_t)(WN_BM + WN_TAPS - 1) * WN_XP * 2 + 255) / 256 * 256 + WN_RING * (size_t)WN_SLAB_BYTES;
-  static unsigned long long raised[2] = {0, 0};
-  const bool f16 = d.compute == TTS_COMPUTE_F16;
-  const void* k = f16 ? reinterpret_cast<const void*>(wavenet_layer_kernel<true>) : reinterpret_cast<const void*>(wavenet_layer_kernel<false>);
-  if (raise_lds_limit(k, raised[f16 ? 1 : 0]) != hipSuccess) {
-    set_error("wavenet_layer: raising the dynamic LDS limit failed");
-    return TTS_E_LAUNCH;
+  if (c) {
+    TTS_CHECK_ARG(c->g && c->wc && c->bc, "wavenet_layer: null conditioning pointer");
+    TTS_CHECK_ARG(c->ld_g >= WN_G && (c->ld_g & 3) == 0 && c->col0 >= 0 && (c->col0 & 31) == 0 && c->col0 + 2 * WN_H <= c->wc_n,
+                  "wavenet_layer: conditioning columns %d .. of %d, row stride %d", c->col0, c->wc_n, c->ld_g);
+    TTS_CHECK_ARG(((uintptr_t)c->g & 15) == 0 && ((uintptr_t)c->wc & 15) == 0 && ((uintptr_t)c->bc & 15) == 0, "wavenet_layer: conditioning operands must be 16-byte aligned");
+  } else {
+    TTS_CHECK_ARG(d.cond, "wavenet_layer: null pointer");
+    TTS_CHECK_ARG((d.ld_cond & 3) == 0 && ((uintptr_t)d.cond & 15) == 0, "wavenet_layer: rows and weights must be 16-byte aligned");
   }
-  if (f16) hipLaunchKernelGGL(wavenet_layer_kernel<true>, dim3(d.n_tiles), dim3(256), lds, st, d);
-  else hipLaunchKernelGGL(wavenet_layer_kernel<false>, dim3(d.n_tiles), dim3(256), lds, st, d);
+  if (d.n_tiles == 0) return TTS_OK;
+  const bool f16 = d.compute == TTS_COMPUTE_F16;
+  const WavenetCond none = {nullptr, 0, nullptr, 0, 0, nullptr};
+  if (c) {
+    const size_t lds = WN_XS_BYTES + WN_GS_BYTES;  // above the 64 KB a kernel gets without asking
+    static unsigned long long raised[2] = {0, 0};
+    const void* k = f16 ? reinterpret_cast<const void*>(wavenet_layer_kernel<true, true>) : reinterpret_cast<const void*>(wavenet_layer_kernel<false, true>);
+    if (raise_lds_limit(k, raised[f16 ? 1 : 0]) != hipSuccess) {
+      set_error("wavenet_layer: raising the dynamic LDS limit failed");
+      return TTS_E_LAUNCH;
+    }
+    if (f16) hipLaunchKernelGGL((wavenet_layer_kernel<true, true>), dim3(d.n_tiles), dim3(256), lds, st, d, *c);
+    else hipLaunchKernelGGL((wavenet_layer_kernel<false, true>), dim3(d.n_tiles), dim3(256), lds, st, d, *c);
+  } else {
+    if (f16) hipLaunchKernelGGL((wavenet_layer_kernel<true, false>), dim3(d.n_tiles), dim3(256), WN_XS_BYTES, st, d, none);
+    else hipLaunchKernelGGL((wavenet_layer_kernel<false, false>), dim3(d.n_tiles), dim3(256), WN_XS_BYTES, st, d, none);
+  }
   return launch_status("wavenet_layer");
 }
+}  // namespace
+
+int wavenet_layer(const TtsWavenetDesc& d, hipStream_t st) { return wavenet_launch(d, nullptr, st); }
+
+int wavenet_layer_cond(const TtsWavenetDesc& d, const WavenetCond& c, hipStream_t st) { return wavenet_launch(d, &c, st); }
 
 }  // namespace tts
 
