@@ -46,6 +46,45 @@ struct ConvW {
       small_only = 0, n_tile = 0, compute16 = 0, algo_taps = 1;
 };
 
+// ---- the model: one field per tensor the stages use, resolved from the weight table once (resolve_acoustic / resolve_vocoder) ----
+struct Block {  // one Conformer block
+  const float *ln_g[5], *ln_b[5];  // norm_ff_macaron, norm_mha, norm_conv, norm_ff, norm_final
+  ConvW ffm1, ffm2, qkv, out, pos, pw1, pw2, ff1, ff2;
+  const float *u, *v, *dw_w, *dw_b;
+  const Dev *ffm_fused = nullptr, *ff_fused = nullptr;  // packing.pack_ffn (16-bit configurations, kernel size 1), or null
+};
+
+struct Predictor {
+  int layers = 0, first_cln = 0;  // conditional layer norms are numbered pitch 0..6, energy 7..8, duration 9..11 (engine.py packs them so)
+  ConvW conv[7], lin;
+  const float *g[7], *b[7];  // plain LayerNorms of the single-speaker checkpoint
+};
+
+struct Acoustic {
+  bool resolved = false;
+  ConvW embed0, embed2;
+  const float* lang_table = nullptr;  // null when absent: an error only where language ids are passed
+  Block enc[6], dec[6];
+  const float *out_norm_g, *out_norm_b;
+  ConvW hs_h, hs_e;  // multi-speaker checkpoints only, like cln_weights
+  const float* cln_weights = nullptr;
+  int n_mlp = 0;
+  Predictor pitch, energy, duration;
+  const float *pitch_w, *pitch_b, *energy_w, *energy_b;
+  ConvW feat_out, g_proj;
+  struct { ConvW conv; const float *g, *b; } postnet[5];
+  struct { ConvW start, end, cond; const float *winv, *an_bias, *an_logs; } flow[18];
+  struct { ConvW inl[4], res_skip[4]; } flowgrp[5];  // in / res-skip layers are shared inside groups of 4 blocks (Glow.py:325-327)
+};
+
+struct Vocoder {
+  bool resolved = false;
+  ConvW pre, ups[4];
+  struct { ConvW c1, c2; const float *a1 = nullptr, *b1 = nullptr, *a2 = nullptr, *b2 = nullptr; } blk[4][3][3];  // snake parameters: BigVGAN only
+  const float *post_w, *post_a = nullptr, *post_b = nullptr, *filt = nullptr;
+  const void* fir_tab = nullptr;
+};
+
 // packed ragged layout: utterance u occupies rows [begins[u], begins[u] + lengths[u])
 struct Layout {
   std::vector<int> begins, lengths;
@@ -128,7 +167,8 @@ struct ProfRec {
 struct Handle {
   TtsConfig cfg;
   std::unordered_map<std::string, Dev> weights;
-  bool resolved = false;
+  Acoustic acoustic;  // resolved at the top of tts_encoder, vocoder at the top of tts_vocoder_*; tts_load_weights unresolves both
+  Vocoder vocoder;
   Arena phone, frame, voc[2];
   TableStore tabs[2][2];          // [0: acoustic stages, 1: vocoder][generation]
   int tab_gen[2] = {0, 0};
@@ -171,6 +211,9 @@ namespace {
   } while (0)
 
 bool is16(const Handle* h);
+
+// the stages after tts_encoder read the model it resolved: a tts_load_weights call since then (it may have freed a tensor) ends the pass
+#define TTS_CHECK_RESOLVED(h, entry) TTS_CHECK_ARG((h)->acoustic.resolved, entry ": weights were loaded since tts_encoder: run it again")
 
 int hip_ok(hipError_t e, const char* what) {
   if (e == hipSuccess) return TTS_OK;
@@ -358,16 +401,19 @@ hipEvent_t prof_event(Handle* h) {
   return e;
 }
 
-bool prof_wants(const Handle* h, const std::string& name) { return h->prof_on && (h->prof_select.empty() || h->prof_select == name); }
-
-ProfRec* prof_open(Handle* h, const std::string& name, double flops, double bytes, double elems, hipStream_t st) {
+// launch() between an event pair on st if the class `name` is being profiled, plainly otherwise; returns launch()'s status
+template <class Launch>
+int prof_launch(Handle* h, const char* name, double flops, double bytes, double elems, hipStream_t st, Launch launch) {
+  if (!h->prof_on || !(h->prof_select.empty() || h->prof_select == name)) return launch();
   h->prof.emplace_back();
   ProfRec* r = &h->prof.back();
   r->name = name; r->flops = flops; r->bytes = bytes; r->elems = elems;
   r->e0 = prof_event(h);
   r->e1 = prof_event(h);
   (void)hipEventRecord(r->e0, st);
-  return r;
+  const int rc = launch();
+  (void)hipEventRecord(r->e1, st);
+  return rc;
 }
 
 // ---- one conv launch (engine.Ops.conv) ----------------------------------------------------------------------------------
@@ -443,29 +489,18 @@ int conv(Handle* h, const ConvW& cw, T2 x, T2 y, const Layout& l, hipStream_t st
                         bm, bn, dual ? ",dual" : "");
     if (h->prof_detail)  // per-shape classes (tools/conv_shapes.py): where the small-GEMM time goes
       snprintf(name + nlen, sizeof(name) - nlen, "[%dx%d k%d r%d]", cw.cin, cw.cout * (dual ? 2 : 1), cw.taps, l.total);
-    if (prof_wants(h, name)) {
-      double rows = 0;
-      for (int n : l.lengths) rows += n;
-      const double ctot = (double)cw.cout * (dual ? 2 : 1);
-      ProfRec* r = prof_open(h, name, 2.0 * rows * cw.cin * ctot * cw.algo_taps,
-                             rows * (cw.cin * (x.bits / 8.0) + cw.cout * (y.bits / 8.0)) + cw.taps * cw.cin * ctot * (d.compute == TTS_COMPUTE_F32 ? 4 : 2),
-                             rows * cw.cout, st);
-      const int rc = tts_conv1d(&d, st);
-      (void)hipEventRecord(r->e1, st);
-      return rc;
-    }
+    double rows = 0;
+    for (int n : l.lengths) rows += n;
+    const double ctot = (double)cw.cout * (dual ? 2 : 1);
+    return prof_launch(h, name, 2.0 * rows * cw.cin * ctot * cw.algo_taps,
+                       rows * (cw.cin * (x.bits / 8.0) + cw.cout * (y.bits / 8.0)) + cw.taps * cw.cin * ctot * (d.compute == TTS_COMPUTE_F32 ? 4 : 2),
+                       rows * cw.cout, st, [&] { return tts_conv1d(&d, st); });
   }
   return tts_conv1d(&d, st);
 }
 
-// ---- model description resolved from the weight table ---------------------------------------------------------------------
-struct Block {
-  const float *ln_g[5], *ln_b[5];  // norm_ff_macaron, norm_mha, norm_conv, norm_ff, norm_final
-  ConvW ffm1, ffm2, qkv, out, pos, pw1, pw2, ff1, ff2;
-  const float *u, *v, *dw_w, *dw_b;
-  const Dev *ffm_fused = nullptr, *ff_fused = nullptr;  // packing.pack_ffn (16-bit configurations, kernel size 1), or null
-};
-
+// ---- the model resolved from the weight table: the only place where tensor names appear ---------------------------------------
+// (the counterpart of native.py's _upload_acoustic / _upload_vocoder; a missing tensor is reported here, before a pass enqueues anything)
 int block_of(const Handle* h, const std::string& p, Block* b) {
   static const char* ln[5] = {"norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff", "norm_final"};
   for (int i = 0; i < 5; ++i) {
@@ -490,6 +525,106 @@ int block_of(const Handle* h, const std::string& p, Block* b) {
   return TTS_OK;
 }
 
+int predictor_of(const Handle* h, const std::string& p, int layers, int first_cln, Predictor* out) {
+  out->layers = layers;
+  out->first_cln = first_cln;
+  for (int i = 0; i < layers; ++i) {
+    TTS_TRY(conv_of(h, p + ".conv." + std::to_string(i), &out->conv[i]));
+    if (h->cfg.multispeaker) continue;  // (conditional layer norms: their scales and shifts come from cln_weights)
+    TTS_TRY(fvec(h, p + ".norm." + std::to_string(i) + ".g", &out->g[i]));
+    TTS_TRY(fvec(h, p + ".norm." + std::to_string(i) + ".b", &out->b[i]));
+  }
+  return conv_of(h, p + ".lin", &out->lin);
+}
+
+int resolve_acoustic(Handle* h) {
+  Acoustic& m = h->acoustic;
+  if (m.resolved) return TTS_OK;
+  TTS_TRY(conv_of(h, "embed0", &m.embed0));
+  TTS_TRY(conv_of(h, "embed2", &m.embed2));
+  const Dev* lang = find(h, "lang_table");
+  m.lang_table = lang ? static_cast<const float*>(lang->p) : nullptr;
+  for (int b = 0; b < 6; ++b) {
+    TTS_TRY(block_of(h, "enc." + std::to_string(b) + ".", &m.enc[b]));
+    TTS_TRY(block_of(h, "dec." + std::to_string(b) + ".", &m.dec[b]));
+  }
+  TTS_TRY(fvec(h, "out_norm.g", &m.out_norm_g));
+  TTS_TRY(fvec(h, "out_norm.b", &m.out_norm_b));
+  if (h->cfg.multispeaker) {
+    TTS_TRY(conv_of(h, "hs_h", &m.hs_h));
+    TTS_TRY(conv_of(h, "hs_e", &m.hs_e));
+    const Dev* w;
+    TTS_TRY(need(h, "cln_weights", &w));
+    m.cln_weights = static_cast<const float*>(w->p);
+    m.n_mlp = (int)(w->bytes / 4 / tts_cln_mlp_weight_floats(64, 256));
+  }
+  TTS_TRY(predictor_of(h, "pitch", 7, 0, &m.pitch));
+  TTS_TRY(predictor_of(h, "energy", 2, 7, &m.energy));
+  TTS_TRY(predictor_of(h, "duration", 3, 9, &m.duration));
+  TTS_TRY(fvec(h, "pitch_w", &m.pitch_w));
+  TTS_TRY(fvec(h, "pitch_b", &m.pitch_b));
+  TTS_TRY(fvec(h, "energy_w", &m.energy_w));
+  TTS_TRY(fvec(h, "energy_b", &m.energy_b));
+  TTS_TRY(conv_of(h, "feat_out", &m.feat_out));
+  for (int i = 0; i < 5; ++i) {
+    const std::string p = "postnet." + std::to_string(i);
+    TTS_TRY(conv_of(h, p + ".conv", &m.postnet[i].conv));
+    TTS_TRY(fvec(h, p + ".g", &m.postnet[i].g));
+    TTS_TRY(fvec(h, p + ".b", &m.postnet[i].b));
+  }
+  TTS_TRY(conv_of(h, "g_proj", &m.g_proj));
+  for (int b = 0; b < 18; ++b) {
+    const std::string p = "flow." + std::to_string(b) + ".";
+    TTS_TRY(conv_of(h, p + "start", &m.flow[b].start));
+    TTS_TRY(conv_of(h, p + "end", &m.flow[b].end));
+    TTS_TRY(conv_of(h, p + "cond", &m.flow[b].cond));
+    TTS_TRY(fvec(h, p + "winv", &m.flow[b].winv));
+    TTS_TRY(fvec(h, p + "an_bias", &m.flow[b].an_bias));
+    TTS_TRY(fvec(h, p + "an_logs", &m.flow[b].an_logs));
+  }
+  for (int g = 0; g < 5; ++g)
+    for (int i = 0; i < 4; ++i) {
+      const std::string p = "flowgrp." + std::to_string(g) + ".";
+      TTS_TRY(conv_of(h, p + "inl." + std::to_string(i), &m.flowgrp[g].inl[i]));
+      TTS_TRY(conv_of(h, p + "res_skip." + std::to_string(i), &m.flowgrp[g].res_skip[i]));
+    }
+  m.resolved = true;
+  return TTS_OK;
+}
+
+int resolve_vocoder(Handle* h) {
+  Vocoder& m = h->vocoder;
+  if (m.resolved) return TTS_OK;
+  const bool big = h->cfg.vocoder == 2;
+  TTS_TRY(conv_of(h, "voc.pre", &m.pre));
+  for (int i = 0; i < 4; ++i) {
+    TTS_TRY(conv_of(h, "voc.ups." + std::to_string(i), &m.ups[i]));
+    for (int j = 0; j < 3; ++j)
+      for (int dd = 0; dd < 3; ++dd) {
+        const std::string p = "voc.blk." + std::to_string(i) + "." + std::to_string(j) + "." + std::to_string(dd);
+        auto& k = m.blk[i][j][dd];
+        TTS_TRY(conv_of(h, p + ".c1", &k.c1));
+        TTS_TRY(conv_of(h, p + ".c2", &k.c2));
+        if (!big) continue;
+        TTS_TRY(fvec(h, p + ".a1", &k.a1));
+        TTS_TRY(fvec(h, p + ".b1", &k.b1));
+        TTS_TRY(fvec(h, p + ".a2", &k.a2));
+        TTS_TRY(fvec(h, p + ".b2", &k.b2));
+      }
+  }
+  TTS_TRY(fvec(h, "voc.post_w", &m.post_w));
+  if (big) {
+    TTS_TRY(fvec(h, "voc.post_a", &m.post_a));
+    TTS_TRY(fvec(h, "voc.post_b", &m.post_b));
+    TTS_TRY(fvec(h, "voc.filt", &m.filt));
+    const Dev* ft;
+    TTS_TRY(need(h, "voc.fir_tab", &ft));
+    m.fir_tab = ft->p;
+  }
+  m.resolved = true;
+  return TTS_OK;
+}
+
 // 16-bit configuration (bf16 / fp16: 16-bit tensors between the fused kernels)?  TTS_COMPUTE_F32X3 is a 32-bit configuration in
 // every respect but the dense products of its frame stages and vocoder (three fp16 MFMAs on split operands)
 bool is16(const Handle* h) { return h->cfg.precision == TTS_COMPUTE_BF16 || h->cfg.precision == TTS_COMPUTE_F16; }
@@ -499,6 +634,7 @@ bool postflow_cond_buffer(const Handle* h) { return !is16(h) || h->no_fused_wave
 
 // relative position tables of both stacks for positions -(pmax-1) .. pmax-1 (Attention.py:177, PositionalEncoding.py:90-130):
 // ptab[s][l][pmax - 1 + p] = linear_pos_l(pe(p)); the sinusoid table "pe" is uploaded by the host (fp32, built like the reference)
+// and looked up here, not resolved with the model: it is uploaded again to grow
 int ensure_ptabs(Handle* h, hipStream_t st) {
   const Dev* pe;
   TTS_TRY(need(h, "pe", &pe));
@@ -513,12 +649,10 @@ int ensure_ptabs(Handle* h, hipStream_t st) {
   const Layout l = Layout::make(&one, 1, 1);
   for (int s = 0; s < 2; ++s)
     for (int b = 0; b < 6; ++b) {
-      ConvW pos;
-      TTS_TRY(conv_of(h, std::string(s ? "dec." : "enc.") + std::to_string(b) + ".pos", &pos));
       ConvOpt o;
       o.fp32_only = true;
       o.no_split_k = true;
-      TTS_TRY(conv(h, pos, T2(pe->p, ATT), T2(h->ptab[s] + (size_t)b * rows * ATT, ATT), l, st, o));
+      TTS_TRY(conv(h, (s ? h->acoustic.dec : h->acoustic.enc)[b].pos, T2(pe->p, ATT), T2(h->ptab[s] + (size_t)b * rows * ATT, ATT), l, st, o));
     }
   h->pmax = pmax;
   return TTS_OK;
@@ -535,16 +669,8 @@ int ffn_fused(Handle* h, const Dev* fused, const ConvW& w1, const ConvW& w2, con
   d.post_g = post_g; d.post_b = post_b;
   d.hidden = (int)(fused->bytes / (28 * 1024)) * 32;
   d.compute = w1.compute16; d.alpha = 0.5f; d.eps = 1e-12f;
-  if (h->prof_on) {
-    const char* name = d.compute == TTS_COMPUTE_F16 ? "ffn_fused_f16" : "ffn_fused_bf16";
-    if (prof_wants(h, name)) {
-      ProfRec* r = prof_open(h, name, 4.0 * R * ATT * d.hidden, (double)R * ATT * 8 + (double)fused->bytes, (double)R * ATT, st);
-      const int rc = tts_ffn_fused(&d, st);
-      (void)hipEventRecord(r->e1, st);
-      return rc;
-    }
-  }
-  return tts_ffn_fused(&d, st);
+  return prof_launch(h, d.compute == TTS_COMPUTE_F16 ? "ffn_fused_f16" : "ffn_fused_bf16", 4.0 * R * ATT * d.hidden,
+                     (double)R * ATT * 8 + (double)fused->bytes, (double)R * ATT, st, [&] { return tts_ffn_fused(&d, st); });
 }
 
 // Layers/EncoderLayer.py:62-144 x 6 on the residual stream x [rows, 192] (already scaled by sqrt(192))
@@ -566,8 +692,7 @@ int conformer(Handle* h, int stack, float* x, const Layout& l, Arena& a, hipStre
   TTS_TRY(tiles_of(h, l, 64, st, &t64));
   const size_t prow = (size_t)(2 * h->pmax - 1) * ATT;
   for (int bi = 0; bi < 6; ++bi) {
-    Block b;
-    TTS_TRY(block_of(h, std::string(stack ? "dec." : "enc.") + std::to_string(bi) + ".", &b));
+    const Block& b = (stack ? h->acoustic.dec : h->acoustic.enc)[bi];
     ConvOpt relu, half, res1;
     relu.act = TTS_ACT_RELU;
     half.alpha = 0.5f; half.res = T2(x, ATT);
@@ -639,7 +764,7 @@ size_t vocoder_arena_bytes(size_t R, int arena, bool fused_mode, bool big) {
 }
 size_t with_growth_slack(size_t bytes) { return bytes + bytes / 8 + (1 << 20); }  // what arena_reserve allocates for a request
 
-int predictor(Handle* h, const char* name, int layers, int first_cln, float* out, hipStream_t st) {
+int predictor(Handle* h, const Predictor& p, float* out, hipStream_t st) {
   const Layout& l = h->lp;
   const int R = l.total;
   TTS_ALLOC(a, h->phone, float, (size_t)R * 256);
@@ -648,30 +773,23 @@ int predictor(Handle* h, const char* name, int layers, int first_cln, float* out
   TTS_TRY(tiles_of(h, l, 64, st, &t64));
   const float* cur = h->enc;
   int ld = ATT;
-  for (int i = 0; i < layers; ++i) {
-    ConvW cw;
-    TTS_TRY(conv_of(h, std::string(name) + ".conv." + std::to_string(i), &cw));
+  for (int i = 0; i < p.layers; ++i) {
     ConvOpt o;
     o.act = TTS_ACT_RELU;
     o.fp32_only = true;
-    TTS_TRY(conv(h, cw, T2(const_cast<float*>(cur), ld), T2(a, 256), l, st, o));
+    TTS_TRY(conv(h, p.conv[i], T2(const_cast<float*>(cur), ld), T2(a, 256), l, st, o));
     if (h->cfg.multispeaker) {
-      const float* sc = h->cln + (size_t)(2 * (first_cln + i)) * h->B * 256;
+      const float* sc = h->cln + (size_t)(2 * (p.first_cln + i)) * h->B * 256;
       TTS_TRY(tts_cond_layernorm(a, 256, bb, 256, sc, sc + (size_t)h->B * 256, 256, t64.dev, t64.n, 64, st));
     } else {
-      const float *g, *b;
-      TTS_TRY(fvec(h, std::string(name) + ".norm." + std::to_string(i) + ".g", &g));
-      TTS_TRY(fvec(h, std::string(name) + ".norm." + std::to_string(i) + ".b", &b));
-      TTS_TRY(tts_layernorm(a, 256, bb, 256, g, b, R, 256, 1e-12f, st));
+      TTS_TRY(tts_layernorm(a, 256, bb, 256, p.g[i], p.b[i], R, 256, 1e-12f, st));
     }
     cur = bb;
     ld = 256;
   }
-  ConvW lin;
-  TTS_TRY(conv_of(h, std::string(name) + ".lin", &lin));
   ConvOpt o;
   o.fp32_only = true;
-  return conv(h, lin, T2(const_cast<float*>(cur), ld), T2(out, 1), l, st, o);
+  return conv(h, p.lin, T2(const_cast<float*>(cur), ld), T2(out, 1), l, st, o);
 }
 
 }  // namespace
@@ -727,6 +845,7 @@ int pipeline_load(Handle* h, const char* name, const void* host, const int64_t* 
     n *= (size_t)shape[i];
   }
   d.bytes = n * esz[dtype];
+  h->acoustic.resolved = h->vocoder.resolved = false;  // (a replaced tensor frees what the model points to: the next pass resolves again)
   auto it = h->weights.find(name);
   if (it != h->weights.end()) {  // replacing a tensor (e.g. a longer position table): nothing may still read the old one
     (void)hipDeviceSynchronize();
@@ -769,6 +888,8 @@ int pipeline_encoder(Handle* h, const float* text, const float* utt_emb, const i
                      hipStream_t st) {
   TTS_CHECK_ARG(h && text && phone_lengths && B > 0, "tts_encoder: bad arguments");
   TTS_CHECK_ARG(!h->cfg.multispeaker || utt_emb, "tts_encoder: the multi-speaker checkpoint needs utterance embeddings");
+  TTS_TRY(resolve_acoustic(h));  // (a missing tensor of any acoustic stage: reported before anything is reserved or enqueued)
+  const Acoustic& m = h->acoustic;
   h->split_mode = 2;
   TTS_TRY(tables_begin(h, 0, st));  // a batch starts: its tile tables go to the acoustic stages' other generation
   h->lp = Layout::make(phone_lengths, B, 1);
@@ -784,45 +905,38 @@ int pipeline_encoder(Handle* h, const float* text, const float* utt_emb, const i
   TTS_ALLOC(e_norm, a, float, (size_t)B * 64);
   h->e_norm = e_norm;
   if (utt_emb) TTS_TRY(tts_l2_normalize(utt_emb, e_norm, B, 64, st));
-  ConvW embed0, embed2;
-  TTS_TRY(conv_of(h, "embed0", &embed0));
-  TTS_TRY(conv_of(h, "embed2", &embed2));
   TTS_ALLOC(h100, a, float, (size_t)R * 100);
   ConvOpt o0;
   o0.act = TTS_ACT_TANH;
   o0.fp32_only = true;
-  TTS_TRY(conv(h, embed0, T2(const_cast<float*>(text), 62), T2(h100, 100), h->lp, st, o0));
+  TTS_TRY(conv(h, m.embed0, T2(const_cast<float*>(text), 62), T2(h100, 100), h->lp, st, o0));
   ConvOpt o2;
   o2.alpha = sqrtf((float)ATT);
   o2.fp32_only = true;
   if (h->cfg.multilingual && lang_ids) {  // Conformer.py:112-114
-    const float* table;
-    TTS_TRY(fvec(h, "lang_table", &table));
+    if (!m.lang_table) {
+      set_error("weight '%s' was not loaded (tts_load_weights)", "lang_table");
+      return TTS_E_ARG;
+    }
     TTS_ALLOC(lang, a, float, (size_t)B * ATT);
-    TTS_TRY(tts_gather_rows(table, ATT, lang_ids, lang, ATT, B, ATT, st));
+    TTS_TRY(tts_gather_rows(m.lang_table, ATT, lang_ids, lang, ATT, B, ATT, st));
     o2.seqvec = lang;
     o2.ld_seqvec = ATT;
   }
   TTS_ALLOC(x, a, float, (size_t)R * ATT);
-  TTS_TRY(conv(h, embed2, T2(h100, 100), T2(x, ATT), h->lp, st, o2));
+  TTS_TRY(conv(h, m.embed2, T2(h100, 100), T2(x, ATT), h->lp, st, o2));
   TTS_TRY(conformer(h, 0, x, h->lp, a, st));
-  const float *g, *b;
-  TTS_TRY(fvec(h, "out_norm.g", &g));
-  TTS_TRY(fvec(h, "out_norm.b", &b));
-  TTS_TRY(tts_layernorm(x, ATT, x, ATT, g, b, R, ATT, 1e-12f, st));
+  TTS_TRY(tts_layernorm(x, ATT, x, ATT, m.out_norm_g, m.out_norm_b, R, ATT, 1e-12f, st));
   if (h->cfg.multispeaker) {  // Conformer.py:130-134: projection of [hidden | normalised utterance embedding]
-    ConvW hs_h, hs_e;
-    TTS_TRY(conv_of(h, "hs_h", &hs_h));
-    TTS_TRY(conv_of(h, "hs_e", &hs_e));
     TTS_ALLOC(e_proj, a, float, (size_t)B * ATT);
     ConvOpt oe;
     oe.fp32_only = true;
-    TTS_TRY(conv(h, hs_e, T2(e_norm, 64), T2(e_proj, ATT), lb, st, oe));
+    TTS_TRY(conv(h, m.hs_e, T2(e_norm, 64), T2(e_proj, ATT), lb, st, oe));
     TTS_ALLOC(enc, a, float, (size_t)R * ATT);
     ConvOpt oh;
     oh.seqvec = e_proj;
     oh.ld_seqvec = ATT;
-    TTS_TRY(conv(h, hs_h, T2(x, ATT), T2(enc, ATT), h->lp, st, oh));
+    TTS_TRY(conv(h, m.hs_h, T2(x, ATT), T2(enc, ATT), h->lp, st, oh));
     h->enc = enc;
   } else {
     h->enc = x;
@@ -835,53 +949,59 @@ int pipeline_encoder(Handle* h, const float* text, const float* utt_emb, const i
   return TTS_OK;
 }
 
+// the scales and shifts of the predictors' conditional layer norms from the utterance embedding (multi-speaker checkpoints)
+int cln_prepare(Handle* h, hipStream_t st) {
+  const Acoustic& m = h->acoustic;
+  TTS_ALLOC(cln, h->phone, float, (size_t)m.n_mlp * h->B * 256);
+  TTS_TRY(tts_cln_mlp(h->e_norm, h->B, 64, 256, m.cln_weights, m.n_mlp, cln, st));
+  h->cln = cln;
+  return TTS_OK;
+}
+
 // ---- stage A.2: pitch / energy / duration predictors (gold values replace a prediction) --------------------------------
 int pipeline_predictors(Handle* h, const float* gold_pitch, const float* gold_energy, const int* gold_dur, hipStream_t st) {
   TTS_CHECK_ARG(h && h->enc, "tts_variance_predictors: run tts_encoder first");
+  TTS_CHECK_RESOLVED(h, "tts_variance_predictors");
   h->split_mode = 2;
   h->tab_which = 0;
-  const int R = h->lp.total, B = h->B;
-  Arena& a = h->phone;
-  if (h->cfg.multispeaker && !(gold_pitch && gold_energy && gold_dur)) {
-    const Dev* w;
-    TTS_TRY(need(h, "cln_weights", &w));
-    const int n_mlp = (int)(w->bytes / 4 / tts_cln_mlp_weight_floats(64, 256));
-    TTS_ALLOC(cln, a, float, (size_t)n_mlp * B * 256);
-    TTS_TRY(tts_cln_mlp(h->e_norm, B, 64, 256, static_cast<const float*>(w->p), n_mlp, cln, st));
-    h->cln = cln;
-  }
-  // conditional layer norms are numbered pitch 0..6, energy 7..8, duration 9..11 (engine.py packs them in this order)
+  const Acoustic& m = h->acoustic;
+  const int R = h->lp.total;
+  if (h->cfg.multispeaker && !(gold_pitch && gold_energy && gold_dur)) TTS_TRY(cln_prepare(h, st));
   if (gold_pitch) TTS_TRY(hip_ok(hipMemcpyAsync(h->pitch, gold_pitch, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold pitch"));
-  else TTS_TRY(predictor(h, "pitch", 7, 0, h->pitch, st));
+  else TTS_TRY(predictor(h, m.pitch, h->pitch, st));
   if (gold_energy) TTS_TRY(hip_ok(hipMemcpyAsync(h->energy, gold_energy, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold energy"));
-  else TTS_TRY(predictor(h, "energy", 2, 7, h->energy, st));
+  else TTS_TRY(predictor(h, m.energy, h->energy, st));
   if (gold_dur) {
     TTS_TRY(hip_ok(hipMemcpyAsync(h->dur, gold_dur, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold durations"));
   } else {
-    TTS_ALLOC(logd, a, float, R);
-    TTS_TRY(predictor(h, "duration", 3, 9, logd, st));
+    TTS_ALLOC(logd, h->phone, float, R);
+    TTS_TRY(predictor(h, m.duration, logd, st));
     TTS_TRY(tts_duration_from_log(logd, h->dur, R, st));
   }
   return TTS_OK;
 }
 
-// ---- stage A.3 / B.0: control, the one host round trip, length regulator -----------------------------------------------
-int pipeline_control_regulate(Handle* h, float duration_scale, float pitch_scale, float energy_scale, float pause_scale,
-                              int* frames_out, hipStream_t st) {
-  TTS_CHECK_ARG(h && h->enc && h->dur, "tts_control_and_regulate: run tts_encoder and tts_variance_predictors first");
-  TTS_CHECK_ARG(duration_scale > 0.f, "tts_control_and_regulate: duration_scaling_factor must be positive");
-  h->tab_which = 0;
+// Per-utterance frame counts from the durations in dur_dev (the one host round trip of a pass), then the frame layout, its arena and
+// the length regulator (LengthRegulator.py:37-61) on h->dur.  gold (teacher forcing): the durations are the caller's, so negative
+// ones and oversized totals are argument errors, and the embeddings are added in the training order - tts_length_regulate forms
+// enc + (first * w1 + b1) + (second * w2 + b2): encoded + energy_embed + pitch_embed there, pitch first at inference.
+int regulate(Handle* h, const int* dur_dev, bool gold, int* frames_out, hipStream_t st) {
+  const Acoustic& m = h->acoustic;
   const int R = h->lp.total, B = h->B;
   const int *pb, *pe;
   TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
-  TTS_TRY(tts_prosody_control(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, duration_scale, pitch_scale, energy_scale, pause_scale, st));
   std::vector<int> d_host(R);
-  TTS_TRY(hip_ok(hipMemcpyAsync(d_host.data(), h->dur, (size_t)R * 4, hipMemcpyDeviceToHost, st), "durations to host"));
+  TTS_TRY(hip_ok(hipMemcpyAsync(d_host.data(), dur_dev, (size_t)R * 4, hipMemcpyDeviceToHost, st), "durations to host"));
   TTS_TRY(hip_ok(hipStreamSynchronize(st), "durations to host: sync"));
   h->frames.assign(B, 0);
   for (int u = 0; u < B; ++u) {
     long long t = 0;
-    for (int i = 0; i < h->lp.lengths[u]; ++i) t += d_host[h->lp.begins[u] + i];
+    for (int i = 0; i < h->lp.lengths[u]; ++i) {
+      const int d = d_host[h->lp.begins[u] + i];
+      TTS_CHECK_ARG(!gold || d >= 0, "tts_teacher_forced: utterance %d, phoneme %d: negative gold duration %d", u, i, d);
+      t += d;
+    }
+    TTS_CHECK_ARG(!gold || t <= (1 << 24), "tts_teacher_forced: utterance %d: %lld frames", u, t);
     h->frames[u] = t > 0 ? (int)t : h->lp.lengths[u];  // LengthRegulator.py:52-53: an all-zero utterance becomes all ones
     if (frames_out) frames_out[u] = h->frames[u];
   }
@@ -894,15 +1014,26 @@ int pipeline_control_regulate(Handle* h, float duration_scale, float pitch_scale
   TTS_ALLOC(dec, a, float, RF * ATT);
   h->cat = cat;
   h->dec = dec;
-  const float *wp, *bp, *we, *be;
-  TTS_TRY(fvec(h, "pitch_w", &wp));
-  TTS_TRY(fvec(h, "pitch_b", &bp));
-  TTS_TRY(fvec(h, "energy_w", &we));
-  TTS_TRY(fvec(h, "energy_b", &be));
   const int *fb, *fe;
   TTS_TRY(bounds_of(h, h->lf, st, &fb, &fe));
-  return tts_length_regulate(h->enc, ATT, h->pitch, h->energy, wp, bp, we, be, h->dur, pb, pe, fb, B, h->lf.max_len, h->lp.max_len, ATT,
-                             cat + 80, 80 + ATT, dec, ATT, sqrtf((float)ATT), st);
+  if (gold)
+    return tts_length_regulate(h->enc, ATT, h->energy, h->pitch, m.energy_w, m.energy_b, m.pitch_w, m.pitch_b, h->dur, pb, pe, fb, B, h->lf.max_len,
+                               h->lp.max_len, ATT, cat + 80, 80 + ATT, dec, ATT, sqrtf((float)ATT), st);
+  return tts_length_regulate(h->enc, ATT, h->pitch, h->energy, m.pitch_w, m.pitch_b, m.energy_w, m.energy_b, h->dur, pb, pe, fb, B, h->lf.max_len,
+                             h->lp.max_len, ATT, cat + 80, 80 + ATT, dec, ATT, sqrtf((float)ATT), st);
+}
+
+// ---- stage A.3 / B.0: control, the one host round trip, length regulator -----------------------------------------------
+int pipeline_control_regulate(Handle* h, float duration_scale, float pitch_scale, float energy_scale, float pause_scale,
+                              int* frames_out, hipStream_t st) {
+  TTS_CHECK_ARG(h && h->enc && h->dur, "tts_control_and_regulate: run tts_encoder and tts_variance_predictors first");
+  TTS_CHECK_ARG(duration_scale > 0.f, "tts_control_and_regulate: duration_scaling_factor must be positive");
+  TTS_CHECK_RESOLVED(h, "tts_control_and_regulate");
+  h->tab_which = 0;
+  const int *pb, *pe;
+  TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
+  TTS_TRY(tts_prosody_control(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, h->B, duration_scale, pitch_scale, energy_scale, pause_scale, st));
+  return regulate(h, h->dur, false, frames_out, st);
 }
 
 // ---- stage A.2 + A.3 with teacher forcing (the scorer): raw predictions, gold prosody, gold durations -----------------------
@@ -911,80 +1042,39 @@ int pipeline_control_regulate(Handle* h, float duration_scale, float pitch_scale
 int pipeline_teacher_forced(Handle* h, const float* gold_pitch, const float* gold_energy, const int* gold_dur, float* pred_log_dur,
                             float* pred_pitch, float* pred_energy, int* frames_out, hipStream_t st) {
   TTS_CHECK_ARG(h && h->enc, "tts_teacher_forced: run tts_encoder first");
+  TTS_CHECK_RESOLVED(h, "tts_teacher_forced");
   TTS_CHECK_ARG(gold_pitch && gold_energy && gold_dur && pred_log_dur && pred_pitch && pred_energy, "tts_teacher_forced: null pointer");
   h->split_mode = 2;
   h->tab_which = 0;
-  const int R = h->lp.total, B = h->B;
-  if (h->cfg.multispeaker) {
-    const Dev* w;
-    TTS_TRY(need(h, "cln_weights", &w));
-    const int n_mlp = (int)(w->bytes / 4 / tts_cln_mlp_weight_floats(64, 256));
-    TTS_ALLOC(cln, h->phone, float, (size_t)n_mlp * B * 256);
-    TTS_TRY(tts_cln_mlp(h->e_norm, B, 64, 256, static_cast<const float*>(w->p), n_mlp, cln, st));
-    h->cln = cln;
-  }
-  // conditional layer norms: pitch 0..6, energy 7..8, duration 9..11 (as in pipeline_predictors)
-  TTS_TRY(predictor(h, "pitch", 7, 0, pred_pitch, st));
-  TTS_TRY(predictor(h, "energy", 2, 7, pred_energy, st));
-  TTS_TRY(predictor(h, "duration", 3, 9, pred_log_dur, st));
+  const Acoustic& m = h->acoustic;
+  const int R = h->lp.total;
+  if (h->cfg.multispeaker) TTS_TRY(cln_prepare(h, st));
+  TTS_TRY(predictor(h, m.pitch, pred_pitch, st));
+  TTS_TRY(predictor(h, m.energy, pred_energy, st));
+  TTS_TRY(predictor(h, m.duration, pred_log_dur, st));
   TTS_TRY(hip_ok(hipMemcpyAsync(h->pitch, gold_pitch, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold pitch"));
   TTS_TRY(hip_ok(hipMemcpyAsync(h->energy, gold_energy, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold energy"));
   TTS_TRY(hip_ok(hipMemcpyAsync(h->dur, gold_dur, (size_t)R * 4, hipMemcpyDeviceToDevice, st), "gold durations"));
-  std::vector<int> d_host(R);
-  TTS_TRY(hip_ok(hipMemcpyAsync(d_host.data(), gold_dur, (size_t)R * 4, hipMemcpyDeviceToHost, st), "durations to host"));
-  TTS_TRY(hip_ok(hipStreamSynchronize(st), "durations to host: sync"));
-  h->frames.assign(B, 0);
-  for (int u = 0; u < B; ++u) {
-    long long t = 0;
-    for (int i = 0; i < h->lp.lengths[u]; ++i) {
-      const int d = d_host[h->lp.begins[u] + i];
-      TTS_CHECK_ARG(d >= 0, "tts_teacher_forced: utterance %d, phoneme %d: negative gold duration %d", u, i, d);
-      t += d;
-    }
-    TTS_CHECK_ARG(t <= (1 << 24), "tts_teacher_forced: utterance %d: %lld frames", u, t);
-    h->frames[u] = t > 0 ? (int)t : h->lp.lengths[u];  // LengthRegulator.py:52-53: an all-zero utterance becomes all ones
-    if (frames_out) frames_out[u] = h->frames[u];
-  }
-  h->lf = Layout::make(h->frames.data(), B, 2);
-  const size_t RF = h->lf.total;
-  TTS_TRY(arena_reserve(h->frame, frame_arena_bytes(RF, postflow_cond_buffer(h)), st));
-  Arena& a = h->frame;
-  TTS_ALLOC(cat, a, float, RF * (80 + ATT));
-  TTS_TRY(hip_ok(hipMemsetAsync(cat, 0, RF * (80 + ATT) * 4, st), "clear frame buffer"));
-  TTS_ALLOC(dec, a, float, RF * ATT);
-  h->cat = cat;
-  h->dec = dec;
-  const float *wp, *bp, *we, *be;
-  TTS_TRY(fvec(h, "pitch_w", &wp));
-  TTS_TRY(fvec(h, "pitch_b", &bp));
-  TTS_TRY(fvec(h, "energy_w", &we));
-  TTS_TRY(fvec(h, "energy_b", &be));
-  const int *pb, *pe, *fb, *fe;
-  TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
-  TTS_TRY(bounds_of(h, h->lf, st, &fb, &fe));
-  // tts_length_regulate forms enc + (first * w1 + b1) + (second * w2 + b2): energy passed first gives the training order
-  // encoded + energy_embed + pitch_embed (the inference order adds pitch first)
-  return tts_length_regulate(h->enc, ATT, h->energy, h->pitch, we, be, wp, bp, h->dur, pb, pe, fb, B, h->lf.max_len, h->lp.max_len, ATT,
-                             cat + 80, 80 + ATT, dec, ATT, sqrtf((float)ATT), st);
+  return regulate(h, gold_dur, true, frames_out, st);
 }
 
 // ---- stage B.1: decoder + feat_out --------------------------------------------------------------------------------------
 int pipeline_decoder(Handle* h, hipStream_t st) {
   TTS_CHECK_ARG(h && h->dec, "tts_decoder: run tts_control_and_regulate first");
+  TTS_CHECK_RESOLVED(h, "tts_decoder");
   h->split_mode = 1;
   h->tab_which = 0;
   TTS_TRY(conformer(h, 1, h->dec, h->lf, h->frame, st));
-  ConvW fo;
-  TTS_TRY(conv_of(h, "feat_out", &fo));
   TTS_ALLOC(mel0, h->frame, float, (size_t)h->lf.total * 80);
   h->mel0 = mel0;
   h->mel = nullptr;
-  return conv(h, fo, T2(h->dec, ATT), T2(mel0, 80), h->lf, st);
+  return conv(h, h->acoustic.feat_out, T2(h->dec, ATT), T2(mel0, 80), h->lf, st);
 }
 
 // ---- stage B.2: PostNet + residual -------------------------------------------------------------------------------------
 int pipeline_postnet(Handle* h, hipStream_t st) {
   TTS_CHECK_ARG(h && h->mel0, "tts_postnet: run tts_decoder first");
+  TTS_CHECK_RESOLVED(h, "tts_postnet");
   h->split_mode = 1;
   h->tab_which = 0;
   const Layout& l = h->lf;
@@ -1000,20 +1090,15 @@ int pipeline_postnet(Handle* h, hipStream_t st) {
   const float* src = h->mel0;
   int ld = 80;
   for (int i = 0; i < 5; ++i) {
-    ConvW cw;
-    const float *g, *b;
-    const std::string p = "postnet." + std::to_string(i);
-    TTS_TRY(conv_of(h, p + ".conv", &cw));
-    TTS_TRY(fvec(h, p + ".g", &g));
-    TTS_TRY(fvec(h, p + ".b", &b));
+    const auto& p = h->acoustic.postnet[i];
     if (i < 4) {
-      TTS_TRY(conv(h, cw, T2(const_cast<float*>(src), ld), T2(x, 256), l, st));
-      TTS_TRY(tts_groupnorm(x, 256, y, 256, g, b, 256, 32, 1e-5f, 1, nullptr, 0, sb, se, l.n(), l.max_len, gws, st));
+      TTS_TRY(conv(h, p.conv, T2(const_cast<float*>(src), ld), T2(x, 256), l, st));
+      TTS_TRY(tts_groupnorm(x, 256, y, 256, p.g, p.b, 256, 32, 1e-5f, 1, nullptr, 0, sb, se, l.n(), l.max_len, gws, st));
       src = y;
       ld = 256;
     } else {
-      TTS_TRY(conv(h, cw, T2(const_cast<float*>(src), ld), T2(y80, 80), l, st));
-      TTS_TRY(tts_groupnorm(y80, 80, h->cat, 80 + ATT, g, b, 80, 20, 1e-5f, 0, h->mel0, 80, sb, se, l.n(), l.max_len, gws, st));
+      TTS_TRY(conv(h, p.conv, T2(const_cast<float*>(src), ld), T2(y80, 80), l, st));
+      TTS_TRY(tts_groupnorm(y80, 80, h->cat, 80 + ATT, p.g, p.b, 80, 20, 1e-5f, 0, h->mel0, 80, sb, se, l.n(), l.max_len, gws, st));
     }
   }
   h->mel = h->cat;  // refined mel, row stride 80 + 192
@@ -1027,16 +1112,16 @@ int pipeline_postnet(Handle* h, hipStream_t st) {
 int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
   TTS_CHECK_ARG(h && h->mel == h->cat && h->cat, "tts_postflow: run tts_postnet first");
   TTS_CHECK_ARG(z_noise, "tts_postflow: z_noise is required");
+  TTS_CHECK_RESOLVED(h, "tts_postflow");
   h->split_mode = 1;
   h->tab_which = 0;
   const Layout ls = h->lf.halved();
   const int RF = h->lf.total, RS = RF / 2;
   Arena& a = h->frame;
   const int b16 = bits16(h);
-  ConvW gp;
-  TTS_TRY(conv_of(h, "g_proj", &gp));
+  const Acoustic& m = h->acoustic;
   TTS_ALLOC(g, a, float, (size_t)RF * ATT);
-  TTS_TRY(conv(h, gp, T2(h->cat, 80 + ATT), T2(g, ATT), h->lf, st));
+  TTS_TRY(conv(h, m.g_proj, T2(h->cat, 80 + ATT), T2(g, ATT), h->lf, st));
   TTS_ALLOC(x, a, float, (size_t)RS * 160);
   TTS_TRY(hip_ok(hipMemcpyAsync(x, z_noise, (size_t)RS * 160 * 4, hipMemcpyDeviceToDevice, st), "flow noise"));
   TTS_ALLOC(hs, a, float, (size_t)RS * 2 * ATT);  // [hidden state | skip sum]
@@ -1067,18 +1152,13 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
   double live_rows = 0;  // (stage profiler)
   for (int n : ls.lengths) live_rows += n;
   for (int b = 17; b >= 0; --b) {
-    const std::string p = "flow." + std::to_string(b) + ".", grp = "flowgrp." + std::to_string(b / 4) + ".";
-    ConvW start, end, cnd;
-    TTS_TRY(conv_of(h, p + "start", &start));
-    TTS_TRY(conv_of(h, p + "end", &end));
-    TTS_TRY(conv_of(h, p + "cond", &cnd));
-    TTS_TRY(conv(h, start, T2(x, 160), T2(hs, 2 * ATT), ls, st));            // h = start(x0); the zero half clears the skip sum
+    const auto& f = m.flow[b];
+    const ConvW& cnd = f.cond;
+    TTS_TRY(conv(h, f.start, T2(x, 160), T2(hs, 2 * ATT), ls, st));            // h = start(x0); the zero half clears the skip sum
     if (!fused) TTS_TRY(conv(h, cnd, T2(g, 2 * ATT), T2(cond, 8 * ATT), ls, st));  // squeeze of g = re-view [RS, 384]
     float* cur = hs;
     for (int i = 0; i < 4; ++i) {
-      ConvW inl, rs;
-      TTS_TRY(conv_of(h, grp + "inl." + std::to_string(i), &inl));
-      TTS_TRY(conv_of(h, grp + "res_skip." + std::to_string(i), &rs));
+      const ConvW &inl = m.flowgrp[b / 4].inl[i], &rs = m.flowgrp[b / 4].res_skip[i];
       if (fused) {
         float* nxt = cur == hs ? hs2 : hs;
         TtsWavenetDesc w;
@@ -1089,16 +1169,12 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
         w.tiles = t64.dev; w.n_tiles = t64.n; w.tile_rows = 64;
         TTS_CHECK_ARG(cnd.w16 && cnd.mode == TTS_MODE_LINEAR && cnd.compute16 == inl.compute16 && cnd.cin == 2 * ATT && cnd.cin_pad == 2 * ATT && cnd.cout == 8 * ATT &&
                           cnd.taps == 1 && cnd.wn >= 8 * ATT,
-                      "tts_postflow: %scond is not a 16-bit 1-tap 384 -> 1536 conv", p.c_str());
+                      "tts_postflow: flow.%d.cond is not a 16-bit 1-tap 384 -> 1536 conv", b);
         const WavenetCond wc = {g, 2 * ATT, cnd.w16, cnd.wn, i * 2 * ATT, cnd.bias};
-        ProfRec* pr = nullptr;
-        if (h->prof_on && prof_wants(h, "wavenet_layer"))  // in-layer, conditioning and res/skip products; state in and out, g, weights
-          pr = prof_open(h, "wavenet_layer", 2.0 * live_rows * (ATT * 5 * 2 * ATT + 2 * ATT * 2 * ATT + (double)ATT * rs.cout),
-                         live_rows * 4.0 * (2 * ATT + rs.cout + 2 * ATT) + 2.0 * (5 * ATT * 2 * ATT + 2 * ATT * 2 * ATT + ATT * rs.cout),
-                         live_rows * rs.cout, st);
-        const int rc = wavenet_layer_cond(w, wc, st);
-        if (pr) (void)hipEventRecord(pr->e1, st);
-        TTS_TRY(rc);
+        // in-layer, conditioning and res/skip products; state in and out, g, weights
+        TTS_TRY(prof_launch(h, "wavenet_layer", 2.0 * live_rows * (ATT * 5 * 2 * ATT + 2 * ATT * 2 * ATT + (double)ATT * rs.cout),
+                            live_rows * 4.0 * (2 * ATT + rs.cout + 2 * ATT) + 2.0 * (5 * ATT * 2 * ATT + 2 * ATT * 2 * ATT + ATT * rs.cout),
+                            live_rows * rs.cout, st, [&] { return wavenet_layer_cond(w, wc, st); }));
         cur = nxt;
         continue;
       }
@@ -1114,12 +1190,8 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
     oe.aux = x + 80;
     oe.ld_aux = 160;
     oe.fp32_only = true;
-    TTS_TRY(conv(h, end, T2(cur + ATT, 2 * ATT), T2(x + 80, 160), ls, st, oe));  // (four fused layers end in `hs` again)
-    const float *winv, *ab, *al;
-    TTS_TRY(fvec(h, p + "winv", &winv));
-    TTS_TRY(fvec(h, p + "an_bias", &ab));
-    TTS_TRY(fvec(h, p + "an_logs", &al));
-    TTS_TRY(tts_glow_invconv_actnorm(x, 160, RS, 160, winv, ab, al, st));
+    TTS_TRY(conv(h, f.end, T2(cur + ATT, 2 * ATT), T2(x + 80, 160), ls, st, oe));  // (four fused layers end in `hs` again)
+    TTS_TRY(tts_glow_invconv_actnorm(x, 160, RS, 160, f.winv, f.an_bias, f.an_logs, st));
   }
   h->mel = x;  // unsqueeze = re-view [2 RS, 80]
   h->have_flow = true;
@@ -1144,6 +1216,8 @@ int pipeline_vocoder(Handle* h, int kind, const float* mel, int ld_mel, const in
                      hipStream_t st) {
   TTS_CHECK_ARG(h && mel && frame_begins && frame_counts && wav && B > 0, "tts_vocoder: bad arguments");
   TTS_CHECK_ARG(kind == h->cfg.vocoder, "tts_vocoder: the handle was created for vocoder %d, not %d", h->cfg.vocoder, kind);
+  TTS_TRY(resolve_vocoder(h));  // (before anything is reserved or enqueued, like the acoustic model in tts_encoder)
+  const Vocoder& m = h->vocoder;
   h->split_mode = 0;
   TTS_TRY(tables_begin(h, 1, st));
   const bool big = kind == 2;
@@ -1165,19 +1239,9 @@ int pipeline_vocoder(Handle* h, int kind, const float* mel, int ld_mel, const in
   TTS_TRY(arena_reserve(h->voc[1], vocoder_arena_bytes(R0, 1, fused_mode, big), st));
   TTS_TRY(arena_reserve(h->voc[0], vocoder_arena_bytes(R0, 0, fused_mode, big), st));
   TTS_ALLOC(x0, h->voc[1], float, R * 512);
-  ConvW pre;
-  TTS_TRY(conv_of(h, "voc.pre", &pre));
-  TTS_TRY(conv(h, pre, T2(const_cast<float*>(mel), ld_mel), T2(x0, 512), l, st));
+  TTS_TRY(conv(h, m.pre, T2(const_cast<float*>(mel), ld_mel), T2(x0, 512), l, st));
   T2 x(x0, 512);
   static const int UP[4] = {8, 6, 4, 2};
-  const float* filt = nullptr;
-  const void* fir_tab = nullptr;
-  if (big) {
-    TTS_TRY(fvec(h, "voc.filt", &filt));
-    const Dev* ft;
-    TTS_TRY(need(h, "voc.fir_tab", &ft));
-    fir_tab = ft->p;
-  }
   int ch = 512;
   for (int i = 0; i < 4; ++i) {
     ch /= 2;
@@ -1188,12 +1252,10 @@ int pipeline_vocoder(Handle* h, int kind, const float* mel, int ld_mel, const in
     Arena& a = h->voc[i & 1];
     const size_t RU = R * u;
     a.reset();  // (sized above; the stage two steps back is dead)
-    ConvW up;
-    TTS_TRY(conv_of(h, "voc.ups." + std::to_string(i), &up));
     TTS_ALLOC(y, a, char, RU * ch * se);
     ConvOpt ou;
     if (!big) { ou.pre = TTS_PRE_LRELU; ou.pre_slope = 0.1f; }
-    TTS_TRY(conv(h, up, x, T2(y, u * ch, sb), l, st, ou));  // transposed conv as a 3-tap polyphase conv; [R, u ch] re-viewed as [R u, ch]
+    TTS_TRY(conv(h, m.ups[i], x, T2(y, u * ch, sb), l, st, ou));  // transposed conv as a 3-tap polyphase conv; [R, u ch] re-viewed as [R u, ch]
     R = RU;
     l = l.scaled(u);
     TTS_ALLOC(stage_out, a, char, R * ch * se);
@@ -1215,22 +1277,17 @@ int pipeline_vocoder(Handle* h, int kind, const float* mel, int ld_mel, const in
     if (fused) TTS_TRY(tiles_of(h, l, tts_resblock_tile_rows(ch), st, &trb));
     if (big && !fused) TTS_TRY(tiles_of(h, l, 256, st, &t256));
     const int f16flag = (sb == 16 && h->cfg.precision == TTS_COMPUTE_F16) ? TTS_IO_F16 : 0;
+    char pname[32];  // (stage profiler)
+    snprintf(pname, sizeof(pname), "resblock_step<%d>", ch);
+    double live_rows = 0;
+    for (int n : l.lengths) live_rows += n;
     for (int j = 0; j < 3; ++j) {
       char* cur = y;
       char* bufs[2] = {buf0, buf1};
       for (int dd = 0; dd < 3; ++dd) {
-        const std::string p = "voc.blk." + std::to_string(i) + "." + std::to_string(j) + "." + std::to_string(dd);
-        ConvW c1, c2;
-        TTS_TRY(conv_of(h, p + ".c1", &c1));
-        TTS_TRY(conv_of(h, p + ".c2", &c2));
+        const auto& k = m.blk[i][j][dd];
+        const ConvW &c1 = k.c1, &c2 = k.c2;
         const bool last = dd == 2;
-        const float *a1 = nullptr, *b1 = nullptr, *a2 = nullptr, *b2 = nullptr;
-        if (big) {
-          TTS_TRY(fvec(h, p + ".a1", &a1));
-          TTS_TRY(fvec(h, p + ".b1", &b1));
-          TTS_TRY(fvec(h, p + ".a2", &a2));
-          TTS_TRY(fvec(h, p + ".b2", &b2));
-        }
         char* dst = last ? stage_out : bufs[dd % 2];
         if (fused) {  // one launch per dilation step: act, conv(dil), act, conv(1), + x (and the stage mean on the last step)
           TtsResblockDesc r;
@@ -1239,21 +1296,11 @@ int pipeline_vocoder(Handle* h, int kind, const float* mel, int ld_mel, const in
           r.c = ch; r.taps = c1.taps; r.dil = c1.dil;
           r.w1 = c1.w16; r.b1 = c1.bias; r.w2 = c2.w16; r.b2 = c2.bias;
           r.act = big ? TTS_PRE_SNAKE : TTS_PRE_LRELU; r.slope = 0.1f;
-          r.alpha1 = a1; r.beta1 = b1; r.alpha2 = a2; r.beta2 = b2; r.filt = filt; r.fir_tab = fir_tab;
+          r.alpha1 = k.a1; r.beta1 = k.b1; r.alpha2 = k.a2; r.beta2 = k.b2; r.filt = m.filt; r.fir_tab = m.fir_tab;
           r.alpha = last ? 1.0f / 3.0f : 1.0f; r.res_scale = r.alpha; r.accumulate = (last && j > 0) ? 1 : 0;
           r.io_bf16 = 1; r.tiles = trb.dev; r.n_tiles = trb.n; r.tile_rows = tts_resblock_tile_rows(ch); r.compute = c1.compute16;
-          char pname[32];
-          snprintf(pname, sizeof(pname), "resblock_step<%d>", ch);
-          if (prof_wants(h, pname)) {
-            double rows = 0;
-            for (int n : l.lengths) rows += n;
-            ProfRec* pr = prof_open(h, pname, 2.0 * rows * ch * ch * c1.taps * 2, 2.0 * rows * ch * se + 2.0 * c1.taps * ch * ch * 2, rows * ch, st);
-            const int rc = tts_resblock_step(&r, st);
-            (void)hipEventRecord(pr->e1, st);
-            if (rc != TTS_OK) return rc;
-          } else {
-            TTS_TRY(tts_resblock_step(&r, st));
-          }
+          TTS_TRY(prof_launch(h, pname, 2.0 * live_rows * ch * ch * c1.taps * 2, 2.0 * live_rows * ch * se + 2.0 * c1.taps * ch * ch * 2, live_rows * ch, st,
+                              [&] { return tts_resblock_step(&r, st); }));
           cur = dst;
           continue;
         }
@@ -1261,9 +1308,9 @@ int pipeline_vocoder(Handle* h, int kind, const float* mel, int ld_mel, const in
         ConvOpt o2;
         if (big) {  // AMP.py:51-60: a1 -> c1 -> a2 -> c2 -> + x with stand-alone anti-aliased snakes
           const int fl = (sb == 16 ? (TTS_IO_X_BF16 | TTS_IO_Y_BF16) : 0) | f16flag;
-          TTS_TRY(tts_snake_aa(reinterpret_cast<const float*>(cur), ch, reinterpret_cast<float*>(sa), ch, a1, b1, filt, ch, t256.dev, t256.n, 256, fl, st));
+          TTS_TRY(tts_snake_aa(reinterpret_cast<const float*>(cur), ch, reinterpret_cast<float*>(sa), ch, k.a1, k.b1, m.filt, ch, t256.dev, t256.n, 256, fl, st));
           TTS_TRY(conv(h, c1, T2(sa, ch, sb), T2(t1, ch, sb), l, st));
-          TTS_TRY(tts_snake_aa(reinterpret_cast<const float*>(t1), ch, reinterpret_cast<float*>(t2), ch, a2, b2, filt, ch, t256.dev, t256.n, 256, fl, st));
+          TTS_TRY(tts_snake_aa(reinterpret_cast<const float*>(t1), ch, reinterpret_cast<float*>(t2), ch, k.a2, k.b2, m.filt, ch, t256.dev, t256.n, 256, fl, st));
           src2 = T2(t2, ch, sb);
         } else {  // ResidualBlock.py:83-98 with LeakyReLU(0.1)
           ConvOpt o1;
@@ -1282,21 +1329,16 @@ int pipeline_vocoder(Handle* h, int kind, const float* mel, int ld_mel, const in
     }
     x = T2(stage_out, ch, sb);
   }
-  const float* pw;
-  TTS_TRY(fvec(h, "voc.post_w", &pw));
   const int xflag = (x.bits == 16 ? TTS_IO_X_BF16 : 0) | ((x.bits == 16 && h->cfg.precision == TTS_COMPUTE_F16) ? TTS_IO_F16 : 0);
   if (big) {
-    const float *pa, *pb;
-    TTS_TRY(fvec(h, "voc.post_a", &pa));
-    TTS_TRY(fvec(h, "voc.post_b", &pb));
     TileTab tp;
     const int tr = tts_conv_post_snake_tile_rows();
     TTS_TRY(tiles_of(h, l, tr, st, &tp));
-    return tts_conv_post_snake(static_cast<const float*>(x.p), ch, ch, pw, h->cfg.post_bias, pa, pb, filt, wav, tp.dev, tp.n, tr, xflag, st);
+    return tts_conv_post_snake(static_cast<const float*>(x.p), ch, ch, m.post_w, h->cfg.post_bias, m.post_a, m.post_b, m.filt, wav, tp.dev, tp.n, tr, xflag, st);
   }
   TileTab tp;
   TTS_TRY(tiles_of(h, l, 256, st, &tp));
-  return tts_conv_post(static_cast<const float*>(x.p), ch, ch, pw, h->cfg.post_bias, TTS_PRE_LRELU, 0.01f, wav, tp.dev, tp.n, 256, xflag, st);  // InferenceAvocodo.py:53
+  return tts_conv_post(static_cast<const float*>(x.p), ch, ch, m.post_w, h->cfg.post_bias, TTS_PRE_LRELU, 0.01f, wav, tp.dev, tp.n, 256, xflag, st);  // InferenceAvocodo.py:53
 }
 
 // the end of every stage entry, whatever its outcome (the extern "C" wrappers): the table generation of `group` that the running batch

@@ -19,6 +19,11 @@ _PRED = (("pitch_predictor", "pitch", 7), ("energy_predictor", "energy", 2), ("d
 _NORMS = ("norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff", "norm_final")
 
 
+def ptr(t):
+    """A tensor's device address as the C ABI takes it (None: NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 class NativePipeline:
     """One handle per (process, device): acoustic model + (optionally) one vocoder."""
 
@@ -257,6 +262,18 @@ class NativePipeline:
             z_sq[b0:b0 + n].copy_(torch.as_tensor(zu, dtype=torch.float32).t()[: 2 * n].reshape(n, 160))
         return z_sq
 
+    def _stage_a(self, packed, duration_scale, pitch_scale, energy_scale, pause_scale, st):
+        """Stage A on a packed batch (tts_encoder, tts_variance_predictors, tts_control_and_regulate): mel frames per utterance."""
+        lib, Ls = self.lib, packed["Ls"]
+        B = len(Ls)
+        self._ensure_pe(max(Ls))
+        capi.check(lib.tts_encoder(self.h, ptr(packed["text"]), ptr(packed["emb"]), ptr(packed["lang"]), (C.c_int32 * B)(*Ls), B, st), "tts_encoder")
+        capi.check(lib.tts_variance_predictors(self.h, ptr(packed["gp"]), ptr(packed["ge"]), ptr(packed["gd"]), st), "tts_variance_predictors")
+        frames = (C.c_int32 * B)()
+        capi.check(lib.tts_control_and_regulate(self.h, float(duration_scale), float(pitch_scale), float(energy_scale), float(pause_scale), frames, st),
+                   "tts_control_and_regulate")
+        return [int(f) for f in frames]
+
     @torch.inference_mode()
     def forward(self, texts, utt_embs, lang_ids=None, durations=None, pitch=None, energy=None, z_noise=None, duration_scaling_factor=1.0,
                 pitch_variance_scale=1.0, energy_variance_scale=1.0, pause_duration_scaling_factor=1.0, run_postflow=True, vocode=True,
@@ -271,17 +288,8 @@ class NativePipeline:
         assert duration_scaling_factor > 0
         if packed is None:
             packed = self.pack_inputs(texts, utt_embs, lang_ids, durations, pitch, energy)
-        Ls, text, emb, lang, gp, ge, gd = (packed[k] for k in ("Ls", "text", "emb", "lang", "gp", "ge", "gd"))
-        B = len(Ls)
-        self._ensure_pe(max(Ls))
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        lens = (C.c_int32 * B)(*Ls)
-        capi.check(lib.tts_encoder(self.h, ptr(text), ptr(emb), ptr(lang), lens, B, st), "tts_encoder")
-        capi.check(lib.tts_variance_predictors(self.h, ptr(gp), ptr(ge), ptr(gd), st), "tts_variance_predictors")
-        frames = (C.c_int32 * B)()
-        capi.check(lib.tts_control_and_regulate(self.h, float(duration_scaling_factor), float(pitch_variance_scale), float(energy_variance_scale),
-                                                float(pause_duration_scaling_factor), frames, st), "tts_control_and_regulate")
-        Ts = [int(f) for f in frames]
+        Ls = packed["Ls"]
+        Ts = self._stage_a(packed, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor, st)
         if max(Ts) > self._pmax:  # longer than the position table: enlarge it and redo the (cheap) phoneme stages
             self._ensure_pe(max(Ts))
             return self.forward(texts, utt_embs, lang_ids, durations, pitch, energy, z_noise, duration_scaling_factor, pitch_variance_scale,
@@ -377,23 +385,9 @@ class NativePipeline:
         """Stage A alone (tts_encoder, tts_variance_predictors, tts_control_and_regulate): mel frames per utterance - the balancing
         key of the multi-GPU deal (distributed.py)."""
         with torch.cuda.device(self.device):
-            dev, lib, st = self.device, self.lib, self._stream()
-            B = len(texts)
-            Ls = [int(t.shape[0]) for t in texts]
-            self._ensure_pe(max(Ls))
-            text = torch.cat([t.reshape(-1, 62).to(torch.float32) for t in texts], dim=0).to(dev).contiguous()
-            emb = utt_embs.to(dev, torch.float32).reshape(B, 64).contiguous() if utt_embs is not None else None
-            lang = torch.tensor([int(i) for i in lang_ids], dtype=torch.int32).to(dev) if (self.multilingual and lang_ids is not None) else None
-            cat = lambda lst: None if lst is None else torch.cat([torch.as_tensor(v).reshape(-1).to(torch.float32) for v in lst]).to(dev).contiguous()
-            gp, ge = cat(pitch), cat(energy)
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-            capi.check(lib.tts_encoder(self.h, ptr(text), ptr(emb), ptr(lang), (C.c_int32 * B)(*Ls), B, st), "tts_encoder")
-            capi.check(lib.tts_variance_predictors(self.h, ptr(gp), ptr(ge), None, st), "tts_variance_predictors")
-            frames = (C.c_int32 * B)()
-            capi.check(lib.tts_control_and_regulate(self.h, float(duration_scaling_factor), float(pitch_variance_scale),
-                                                    float(energy_variance_scale), float(pause_duration_scaling_factor), frames, st),
-                       "tts_control_and_regulate")
-            return [int(f) for f in frames]
+            packed = self.pack_inputs(texts, utt_embs, lang_ids, None, pitch, energy)
+            return self._stage_a(packed, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor,
+                                 self._stream())
 
     @torch.inference_mode()
     def vocode_batch(self, rag_mel):

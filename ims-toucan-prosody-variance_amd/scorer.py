@@ -253,7 +253,7 @@ class TTSScorer:
             mark("acoustic")
             packed = pipe.pack_inputs([torch.from_numpy(it["text"]) for it in items], embs, [lang_id] * B,
                                       [it["durations"] for it in items], [it["pitch"] for it in items], [it["energy"] for it in items])
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            ptr = native.ptr
             capi.check(lib.tts_encoder(pipe.h, ptr(packed["text"]), ptr(packed["emb"]), ptr(packed["lang"]), (C.c_int32 * B)(*Ls), B, st),
                        "tts_encoder")
             R = sum(Ls)

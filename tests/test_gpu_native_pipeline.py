@@ -277,3 +277,68 @@ def test_fresh_layouts_build_tables_and_replayed_batches_build_none():
     replayed find all their tables in the generation that kept them: nothing is built or uploaded, and the bits are the same."""
     for kind in ("hifigan", "bigvgan"):
         _fresh_layouts_then_replay(kind)
+
+
+def _without(*names):
+    """NativePipeline whose upload leaves the tensors `names` out."""
+    class Dropping(native.NativePipeline):
+        def _load(self, name, t):
+            if name not in names:
+                super()._load(name, t)
+    return Dropping
+
+
+def test_a_missing_late_stage_tensor_is_reported_up_front():
+    """The model is resolved at the first stage entry of a pass: a handle that lacks a tensor of the LAST acoustic stage (PostFlow)
+    fails in tts_encoder, one that lacks a tensor of the vocoder's last residual block at the top of tts_vocoder_hifigan - both by
+    name, and before anything was reserved or launched (the handle's arenas are still empty)."""
+    texts, embs, langs, _ = _inputs([_gold("L7_pred")])
+    pipe = _without("flow.17.winv", "voc.blk.3.2.2.c2.w")(fw.acoustic_state_dict(), fw.hifigan_state_dict(), "hifigan", DEV)
+    lib, st = pipe.lib, torch.cuda.current_stream().cuda_stream
+    packed = pipe.pack_inputs(texts, embs, langs)
+    lens = (C.c_int32 * 1)(*packed["Ls"])
+    assert packed["Ls"] == [7]
+    assert lib.tts_encoder(pipe.h, native.ptr(packed["text"]), native.ptr(packed["emb"]), native.ptr(packed["lang"]), lens, 1, st) != 0
+    err = lib.tts_last_error()
+    assert b"flow.17.winv" in err and b"was not loaded" in err, err
+    assert int(lib.tts_workspace_claimed(pipe.h)) == 0
+    mel = torch.zeros(7, 80, device=DEV)
+    wav = torch.empty(7 * 384, device=DEV)
+    fb, fc = (C.c_int32 * 1)(0), (C.c_int32 * 1)(7)
+    assert lib.tts_vocoder_hifigan(pipe.h_voc, native.ptr(mel), 80, fb, fc, 1, native.ptr(wav), st) != 0
+    err = lib.tts_last_error()
+    assert b"voc.blk.3.2.2.c2.w" in err and b"was not loaded" in err, err
+    assert int(lib.tts_workspace_claimed(pipe.h_voc)) == 0
+
+
+def test_a_re_uploaded_tensor_is_resolved_again():
+    """tts_load_weights on a name the handle holds frees the old allocation: the next pass must resolve the model again.  A pass,
+    out_norm.b + 0.5 uploaded over the old one, a pass: the mel of a fresh pipeline built with that bias, bit for bit; the original
+    uploaded again: the first mel, bit for bit."""
+    texts, embs, langs, _ = _inputs([_gold("L7_pred")])
+    sd = fw.acoustic_state_dict()
+    key = "encoder.output_norm.bias"
+    shifted = sd[key] + np.float32(0.5)
+    # (seeded noise, not the golden's: the shifted bias may change the predicted frame count)
+    run = lambda p: p.forward(texts, embs, langs, generator=torch.Generator(device=DEV).manual_seed(5))["mel"][0].clone()
+    pipe = native.NativePipeline(sd, None, None, DEV)
+    first = run(pipe)
+    pipe._load("out_norm.b", torch.from_numpy(shifted))
+    second = run(pipe)
+    assert not torch.equal(second, first)
+    assert torch.equal(second, run(native.NativePipeline(dict(sd, **{key: shifted}), None, None, DEV)))
+    pipe._load("out_norm.b", torch.from_numpy(sd[key]))
+    assert torch.equal(run(pipe), first)
+
+
+def test_predict_frame_counts_is_stage_a_of_forward():
+    """predict_frame_counts (the multi-GPU deal's balancing key) and forward() share stage A: same frame counts, with the default
+    controls and with all four scales."""
+    us, Ls = [300, 301, 302], [48, 21, 33]
+    feats = [torch.from_numpy(syn.utterance_features(u, L)) for u, L in zip(us, Ls)]
+    embs = torch.from_numpy(np.stack([syn.utterance_embedding(u) for u in us]))
+    langs = [syn.LANG_EN] * 3
+    pipe = native.NativePipeline(fw.acoustic_state_dict(), None, None, DEV)
+    for kw in ({}, dict(duration_scaling_factor=0.9, pitch_variance_scale=1.2, energy_variance_scale=0.8, pause_duration_scaling_factor=1.3)):
+        want = [int(n) for n in pipe.forward(feats, embs, langs, vocode=False, **kw)["rag_frame"].lengths]
+        assert pipe.predict_frame_counts(feats, embs, langs, **kw) == want and len(want) == 3 and min(want) > 0, kw
