@@ -19,8 +19,6 @@
 //     register r of a lane is key (r&3)+8(r>>2)+4hi, so "k-pair r" of the product pairs keys (base_r, base_r+4) and the
 //     A operand V^T is simply read from LDS with that key order.  No transpose, no conversion.
 //   * keys beyond the utterance get -inf; queries beyond it are computed and discarded.
-#include <cstdlib>
-
 #include "common.h"
 
 namespace tts {
@@ -469,8 +467,7 @@ int relpos_attention_mfma(const float* qkv, int ld_qkv, const float* ptab, int p
   // the CALLER chooses (include/toucan_tts.h): never (flags 0: the fp32 layers of the 16-bit configurations, whose results are
   // bit for bit independent of the batch), on small grids (TTS_ATT_KEY_SPLIT: the decoder of the fp32 configuration) or always
   // (TTS_ATT_KEY_SPLIT_ALWAYS: its encoder - upstream of the rounded durations, one arithmetic whatever the batch)
-  const bool split = ((flags & TTS_ATT_KEY_SPLIT_ALWAYS) || ((flags & TTS_ATT_KEY_SPLIT) && (long long)n_tiles * heads <= 64)) &&
-                     std::getenv("TOUCAN_NO_ATTENTION_SPLIT") == nullptr;
+  const bool split = (flags & TTS_ATT_KEY_SPLIT_ALWAYS) || ((flags & TTS_ATT_KEY_SPLIT) && (long long)n_tiles * heads <= 64);
   const size_t lds = (size_t)(2 * (split ? 4 : 1) * AM_KT * AM_PITCH + (AM_PW + 1) * AM_PITCH + 4 * 64 * AM_GP) * sizeof(float);
   if (split) {
     static unsigned long long lds_raised = 0;  // per device (common.h)

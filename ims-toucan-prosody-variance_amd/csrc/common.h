@@ -108,6 +108,17 @@ __device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
   else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// Operand streams written with inline-asm loads and hand-counted waits (conv1d.hip: the 1-tap rows form and the split-K form;
+// wavenet.hip: the weight stream): the loads return in order, so before k-step s is consumed exactly (DEPTH-1) * L younger loads
+// may stay in flight (L = loads per k-step).  Left to the compiler the same loop either had its 16-byte loads split into dwords
+// (the fragments are consumed lane-element by lane-element) or drained every outstanding load at the loop head (it cannot count
+// across the back edge); the asm is invisible to its counters, and each wait is followed by empty asm statements that
+// "redefine" the registers just waited for (TTS_PIN), so no use can move above it.
+#define TTS_GLOAD128(dst_, ptr_) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst_) : "v"(ptr_) : "memory")
+#define TTS_GLOAD32(dst_, ptr_) asm volatile("global_load_dword %0, %1, off" : "=v"(dst_) : "v"(ptr_) : "memory")
+#define TTS_WAIT_VM(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
+#define TTS_PIN(r_) asm volatile("" : "+v"(r_))
+
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
 __device__ __forceinline__ float wave_sum(float v) {

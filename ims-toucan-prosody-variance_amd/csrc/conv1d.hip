@@ -24,16 +24,11 @@
 // vector, pre-add, activation, GLU / gated / coupling, residual, accumulate, 16-bit I/O) behind conv_epilogue_t / conv_epilogue16_t.
 //
 // Reference ops replaced: see include/toucan_tts.h (tts_conv1d).
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
 #include "snake.h"
-
-#ifndef CONV_DIAG
-#define CONV_DIAG 0  // diagnostic builds of conv1d_kernel (tools/build_variant.sh NAME -DCONV_DIAG=n): 1 no epilogue, 2 no MFMAs, 3 window staged for slab 0 only, 4 weight slab loaded once, 5 16-bit output wrapped into 1 024 rows, 6 per-workgroup clock stamps (tts_conv_diag_trace)
-#endif
 
 namespace tts {
 
@@ -92,15 +87,6 @@ struct Elem<false, F16> {
   using T = float;
   static __device__ __forceinline__ float cvt(float v) { return v; }
 };
-
-#if CONV_DIAG == 6
-__device__ unsigned long long g_conv_trace[4096][4];
-}  // namespace tts
-extern "C" int tts_conv_diag_trace(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(tts::g_conv_trace), sizeof(unsigned long long) * 4096 * 4) == hipSuccess ? 0 : -1;
-}
-namespace tts {
-#endif
 
 // compile-time loop: f(integral_constant<int, K>) for K = K0 .. N-1
 template <int K, int N, class F>
@@ -178,7 +164,8 @@ __device__ __forceinline__ bool epilogue_vec_ok(const TtsConvDesc& d) {
 // residual, accumulate and the store move 8 (16-bit tensors) or 16 (fp32) bytes at a time.  (With the output channel on the lane -
 // the untransposed layout - a 128 x 128 tile left through 64 two-byte stores per lane: 58 us of a 147 us launch at 256 -> 256
 // channels x 3 taps, 122 of 211 us with a residual read the same way, 340 of 609 us in the 128 -> 256 up-sampler; measured with
-// -DCONV_DIAG=1.)  A row's pieces are written by one wavefront within a few hundred cycles: L2 merges them into whole lines.
+// a diagnostic build that skipped the epilogue)  A row's pieces are written by one wavefront within a few
+// hundred cycles: L2 merges them into whole lines.
 template <int TM, int TN, int NH, bool DUAL>
 __device__ __forceinline__ void conv_epilogue_t(const TtsConvDesc& d, const TtsTile& tile, int n0, int wm, int wn, int lrow, int lk,
                                                 const f32x16 (&acc)[NH][TM][TN], const float* eb = nullptr, int eb_n = 0) {
@@ -188,7 +175,7 @@ __device__ __forceinline__ void conv_epilogue_t(const TtsConvDesc& d, const TtsT
   if constexpr (!DUAL) {
     if (vec && !d.preadd && eb) {
       // The common case (plain convs: bias, per-utterance vector, residual, accumulate).  What was measured on the 128 x 128 tile at
-      // 256 -> 256 channels (clock stamps, -DCONV_DIAG=6): main loop 41.7 k cycles, epilogue 21.9 k - not the stores (they drain in
+      // 256 -> 256 channels (clock stamps of a diagnostic build): main loop 41.7 k cycles, epilogue 21.9 k - not the stores (they drain in
       // 0.4 k), but sixteen dependent global-load round trips per lane (bias, vector, residual of each 4-channel group, each ~1.4 k
       // cycles, and behind earlier stores: loads and stores share the in-order vmcnt counter, so a load issued after a store is usable
       // only once that store is acknowledged).  Hence: bias and per-utterance vector come from LDS (`eb`, staged at kernel start), and
@@ -249,11 +236,7 @@ __device__ __forceinline__ void conv_epilogue_t(const TtsConvDesc& d, const TtsT
             float v3 = epilogue_value<false>(d, acc[0][i][j][4 * rq + 3], 0.f, ba.w, 0.f, sv.w, 0.f, 0.f, 0.f, r4.w);
             if (d.accumulate) { v0 += y4.x; v1 += y4.y; v2 += y4.z; v3 += y4.w; }
             if (y16) {
-#if CONV_DIAG == 5  // diagnostic: the output lands in 1 024 rows over and over (stays in L2: no HBM write stream)
-              uint2* yp = reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(d.y) + (size_t)(row & 1023) * d.ldy + n);
-#else
               uint2* yp = reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(d.y) + (size_t)row * d.ldy + n);
-#endif
               *yp = make_uint2((unsigned int)store16(v0, io_f16) | ((unsigned int)store16(v1, io_f16) << 16),
                                (unsigned int)store16(v2, io_f16) | ((unsigned int)store16(v3, io_f16) << 16));
             } else {
@@ -418,9 +401,6 @@ void conv1d_kernel(const TtsConvDesc d) {
   constexpr int UPT = UNITS / 256;                  // units per thread
   static_assert(UNITS % 256 == 0, "slab must split evenly over the workgroup");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-#if CONV_DIAG == 6
-  const unsigned long long diag_t0 = __builtin_amdgcn_s_memtime();
-#endif
 
   const TtsTile tile = d.tiles[blockIdx.x];
   const int n0 = blockIdx.y * BN;  // first output column (within a half in dual mode)
@@ -601,9 +581,6 @@ void conv1d_kernel(const TtsConvDesc d) {
     const int kchunk = (d.cin_pad - c0) < BK ? (d.cin_pad - c0) : BK;
     ET* xs = xs0 + ((win2 && (ch & 1)) ? xs_elems : 0);
     if (!win2 && ch > 0) __syncthreads();  // the previous slab's MFMAs are done with xs
-#if CONV_DIAG == 3
-    if (ch == 0) {
-#endif
     // ---- stage the activation window: win_rows x kchunk channels, through the input activation ----
     if (win2) {
       // already in LDS (committed at the end of the previous slab); request the next one now, it lands under this slab's MFMAs
@@ -747,17 +724,10 @@ void conv1d_kernel(const TtsConvDesc d) {
         }
       }
     }
-#if CONV_DIAG == 3
-    }
-#endif
     for (int tap = 0; tap < d.taps; ++tap, ++step) {
       __syncthreads();  // xs and ws[step&1] visible; everybody is done reading ws[(step+1)&1]
       const bool more = step + 1 < total_steps;
-#if CONV_DIAG == 4
-      if (false) {
-#else
       if (more) {
-#endif
         const int ntap = tap + 1 < d.taps ? tap + 1 : 0;
         const int nc0 = tap + 1 < d.taps ? c0 : c0 + BK;
         const int nk = (d.cin_pad - nc0) < BK ? (d.cin_pad - nc0) : BK;
@@ -785,11 +755,7 @@ void conv1d_kernel(const TtsConvDesc d) {
             for (int i = 0; i < TM; ++i)
 #pragma unroll
               for (int j = 0; j < TN; ++j) {
-#if CONV_DIAG == 2
-                asm volatile("" ::"v"(a[i]), "v"(b[j]));
-#else
                 acc[h][i][j] = mfma16<F16>(b[j], a[i], acc[h][i][j]);  // transposed: weights = A operand, the lane keeps a ROW (conv_epilogue_t)
-#endif
                 if constexpr (X3) {
                   accx[h][i][j] = mfma16<true>(bl[j], a[i], accx[h][i][j]);
                   accx[h][i][j] = mfma16<true>(b[j], al[i], accx[h][i][j]);
@@ -836,30 +802,7 @@ void conv1d_kernel(const TtsConvDesc d) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[h][i][j][r] = fmaf(accx[h][i][j][r], 1.0f / 2048.0f, acc[h][i][j][r]);
   }
-#if CONV_DIAG == 6  // diagnostic: per-workgroup clocks (start, main loop done, epilogue issued, epilogue drained) of wavefront 0
-  const unsigned long long diag_t1 = __builtin_amdgcn_s_memtime();
   conv_epilogue_t<TM, TN, NH, DUAL>(d, tile, n0, wm, wn, lrow, lk, acc, eb, BN);
-  const unsigned long long diag_t2 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const unsigned long long diag_t3 = __builtin_amdgcn_s_memtime();
-  if (threadIdx.x == 0) {
-    const unsigned int slot = (blockIdx.y * gridDim.x + blockIdx.x) & 4095;
-    g_conv_trace[slot][0] = diag_t0; g_conv_trace[slot][1] = diag_t1; g_conv_trace[slot][2] = diag_t2; g_conv_trace[slot][3] = diag_t3;
-  }
-#elif CONV_DIAG == 1
-  {  // diagnostic build: no epilogue (one never-taken store keeps the accumulators alive)
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += acc[0][i][j][r];
-    if (t == 1.2345e-30f) d.y[0] = t;
-  }
-#else
-  conv_epilogue_t<TM, TN, NH, DUAL>(d, tile, n0, wm, wn, lrow, lk, acc, eb, BN);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -890,18 +833,10 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const TtsConvDesc d) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[h][0][0][r] = 0.0f;
 
-  // The operand stream is written with inline-asm loads and hand-counted waits: the loads return in order, so before k-step s
-  // is consumed exactly (DEPTH-1) * L younger loads may stay in flight (L = loads per k-step).  Left to the compiler the same
-  // loop either had its 16-byte loads split into dwords (the fragments are consumed lane-element by lane-element) or drained
-  // every outstanding load at the loop head (it cannot count across the back edge); the asm is invisible to its counters, and
-  // each wait is followed by empty asm statements that "redefine" the registers just waited for, so no use can move above it.
+  // (the operand stream: inline-asm loads and hand-counted waits, see TTS_GLOAD128 in common.h)
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   // (by value: __builtin_bit_cast applied directly to an element of an ext-vector reads element 0 whatever the index)
   auto u2f = [](unsigned int bits) __attribute__((always_inline)) { return __builtin_bit_cast(float, bits); };
-#define TTS_GLOAD128(dst_, ptr_) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst_) : "v"(ptr_) : "memory")
-#define TTS_GLOAD32(dst_, ptr_) asm volatile("global_load_dword %0, %1, off" : "=v"(dst_) : "v"(ptr_) : "memory")
-#define TTS_WAIT_VM(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
-#define TTS_PIN(r_) asm volatile("" : "+v"(r_))
   if constexpr (BF16) {
     const int n_steps = d.cin_pad >> 4;  // multiple of DEPTH (dispatch guarantees cin % 64 == 0)
     constexpr int L = (XB ? 1 : 2) + NH;
@@ -1021,10 +956,6 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const TtsConvDesc d) {
         for (int j = 0; j < 4; ++j) TTS_PIN(b[h][u][j]);
     }
   }
-#undef TTS_GLOAD128
-#undef TTS_GLOAD32
-#undef TTS_WAIT_VM
-#undef TTS_PIN
   conv_epilogue_t<1, 1, NH, DUAL>(d, tile, n0, wm, wn, lrow, lk, acc);
 }
 
@@ -1058,10 +989,7 @@ __global__ __launch_bounds__(256) void conv_splitk_f32_kernel(const TtsConvDesc 
   constexpr int NA = T16 ? 1 : 2;    // float4 activation loads per lane and k-step (T16: 4 k-slots x 4 channels; 32 x 32: 2 k-slots x 4 channels, twice)
   constexpr int NB = 4 * NA;         // weight dwords per lane, half and k-step
   constexpr int AR = T16 ? 4 : 16;   // accumulator registers per lane
-#ifndef TTS_SPLITK_DEPTH
-#define TTS_SPLITK_DEPTH 4
-#endif
-  constexpr int DEPTH = T16 ? TTS_SPLITK_DEPTH : TTS_SPLITK_DEPTH / 2;  // k-steps in flight per wavefront (the same bytes either way; 4, 6, 8 measured alike)
+  constexpr int DEPTH = T16 ? 4 : 2;  // k-steps in flight per wavefront (the same bytes either way; 4, 6, 8 measured alike)
   constexpr int L = NA + NB * NH;    // loads per k-step
   static_assert((DEPTH - 1) * L <= 63, "vmcnt is a 6-bit count");
   using Acc = typename std::conditional<T16, f32x4, f32x16>::type;
@@ -1084,10 +1012,6 @@ __global__ __launch_bounds__(256) void conv_splitk_f32_kernel(const TtsConvDesc 
 
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   auto u2f = [](unsigned int bits) __attribute__((always_inline)) { return __builtin_bit_cast(float, bits); };
-#define TTS_GLOAD128(dst_, ptr_) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst_) : "v"(ptr_) : "memory")
-#define TTS_GLOAD32(dst_, ptr_) asm volatile("global_load_dword %0, %1, off" : "=v"(dst_) : "v"(ptr_) : "memory")
-#define TTS_WAIT_VM(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
-#define TTS_PIN(r_) asm volatile("" : "+v"(r_))
   const int G = d.cin / GC;                       // k-steps per tap (dispatch: cin % 16 == 0, cin >= 32)
   const int S = d.taps * G;                       // k-steps of the whole contraction
   const int n_w = S > wave ? (S - wave + 3) >> 2 : 0;  // ... of this wavefront: s = wave, wave + 4, ...
@@ -1169,10 +1093,6 @@ __global__ __launch_bounds__(256) void conv_splitk_f32_kernel(const TtsConvDesc 
 #pragma unroll
       for (int j = 0; j < NB; ++j) TTS_PIN(b[h][u][j]);
   }
-#undef TTS_GLOAD128
-#undef TTS_GLOAD32
-#undef TTS_WAIT_VM
-#undef TTS_PIN
   if (wave != 0) {
 #pragma unroll
     for (int h = 0; h < NH; ++h)
@@ -1289,7 +1209,7 @@ static bool gemm_rows_ok(const TtsConvDesc& d) {
     if ((long long)d.n_tiles * (cols / 64) > 256) return false;
   }
   if ((d.ldx & (xb ? 7 : 3)) != 0 || (reinterpret_cast<uintptr_t>(d.x) & 15) != 0) return false;
-  return std::getenv("TOUCAN_NO_GEMM_ROWS") == nullptr;  // escape hatch for A/B measurements
+  return true;
 }
 
 // the split-K form: fp32, opted in by the caller.  TTS_IO_SPLIT_K: a grid of at most 128 workgroups if cut into 64 x 64 tiles and a
@@ -1299,17 +1219,16 @@ static bool gemm_rows_ok(const TtsConvDesc& d) {
 static bool splitk_ok(const TtsConvDesc& d, int cols) {
   if (d.compute != 0 || !(d.io_flags & (TTS_IO_SPLIT_K | TTS_IO_SPLIT_K_ALWAYS)) || (d.io_flags & TTS_IO_X_BF16) || d.pre_act == TTS_PRE_SNAKE) return false;
   if ((d.cin & 15) != 0 || d.cin < 32 || (d.ldx & 3) != 0 || (reinterpret_cast<uintptr_t>(d.x) & 15) != 0 || (cols & 31) != 0) return false;
-  static const int min_depth = std::getenv("TOUCAN_SPLIT_K_MIN") ? std::atoi(std::getenv("TOUCAN_SPLIT_K_MIN")) : 64;  // (A/B runs)
-  static const int max_grid = std::getenv("TOUCAN_SPLIT_K_GRID") ? std::atoi(std::getenv("TOUCAN_SPLIT_K_GRID")) : 128;  // (A/B runs)
+  constexpr int min_depth = 64, max_grid = 128;  // (measured, see above)
   if ((long long)d.taps * d.cin < min_depth) return false;
   if (!(d.io_flags & TTS_IO_SPLIT_K_ALWAYS) && (long long)d.n_tiles * (d.tile_rows / 64) * ((cols + 63) / 64) > max_grid) return false;
-  return std::getenv("TOUCAN_NO_SPLIT_K") == nullptr;  // escape hatch for A/B measurements
+  return std::getenv("TOUCAN_NO_SPLIT_K") == nullptr;  // (read at every launch: tests/test_gpu_kernels.py flips it inside one process)
 }
 
 static int launch_splitk(const TtsConvDesc& d, int cols, hipStream_t st) {
   const bool dual = d.mode != TTS_MODE_LINEAR;
   // 16 x 16 tiles while the 32 x 32 grid is at most 128 workgroups (a speed choice only: both sizes sum in the same order)
-  if (d.cin >= 64 && (long long)d.n_tiles * (d.tile_rows / 32) * (cols / 32) <= (std::getenv("TOUCAN_SPLIT_K16_GRID") ? std::atoi(std::getenv("TOUCAN_SPLIT_K16_GRID")) : 128) && std::getenv("TOUCAN_NO_SPLIT_K16") == nullptr) {
+  if (d.cin >= 64 && (long long)d.n_tiles * (d.tile_rows / 32) * (cols / 32) <= 128 && std::getenv("TOUCAN_NO_SPLIT_K16") == nullptr) {
     dim3 grid(d.n_tiles * (d.tile_rows / 16), cols / 16), block(256);
     if (dual) hipLaunchKernelGGL((conv_splitk_f32_kernel<true, true>), grid, block, 0, st, d);
     else hipLaunchKernelGGL((conv_splitk_f32_kernel<false, true>), grid, block, 0, st, d);
@@ -1362,9 +1281,6 @@ int conv1d_dispatch(const TtsConvDesc& d, hipStream_t st) {
   TTS_CHECK_ARG(d.tile_rows == bm, "conv1d: tile table built for %d rows, kernel needs %d", d.tile_rows, bm);
   TTS_CHECK_ARG(cols % bn == 0 && cols >= d.cout, "conv1d: packed width %d not a multiple of the N tile %d (cout %d)", cols, bn, d.cout);
   TTS_CHECK_ARG(d.mode == TTS_MODE_LINEAR || d.wn == 2 * d.half_pad, "conv1d: dual mode needs wn == 2*half_pad");
-  if (d.compute == 0 && std::getenv("TOUCAN_SPLIT_K_LOG"))  // (debugging aid: which form every fp32 launch takes)
-    fprintf(stderr, "conv-f32 cin %d cout %d taps %d tile_rows %d tiles %d cols %d ldx %d flag %d -> splitk %d\n", d.cin, d.cout, d.taps, d.tile_rows,
-            d.n_tiles, cols, d.ldx, (int)((d.io_flags & TTS_IO_SPLIT_K) != 0), (int)splitk_ok(d, cols));
   if (splitk_ok(d, cols)) return launch_splitk(d, cols, st);  // (whatever the table's tile rows: the kernel cuts its own row blocks out of them)
   if ((s == S_64x64 || s == S_D64x64) && gemm_rows_ok(d)) return launch_gemm_rows(d, st);
   // Small-batch form with 128-column tiles (four wavefronts side by side) once the grid fills the chip anyway: wide outputs

@@ -180,9 +180,6 @@ struct Handle {
                                   // of them keeps one arithmetic whatever the batch (an utterance's frame count cannot depend on the batch or
                                   // shard it is in); 1 (frame stages): the split forms on small grids only (TTS_IO_SPLIT_K / TTS_ATT_KEY_SPLIT:
                                   // the mel agrees to rounding order across batch sizes); 0 (vocoder: chunked == whole, bit for bit)
-  bool no_fused_wavenet = false;  // TOUCAN_NO_FUSED_WAVENET: A/B switch, same meaning as in engine.py
-  bool no_fused_ffn = false;      // TOUCAN_NO_FUSED_FFN: likewise
-  bool no_f16_attention = false;  // TOUCAN_NO_F16_ATTENTION: likewise
   // relative position tables [block][2 pmax - 1][192] of the two Conformer stacks, built from the uploaded sinusoid table
   float* ptab[2] = {nullptr, nullptr};
   int pmax = 0;
@@ -629,8 +626,8 @@ int resolve_vocoder(Handle* h) {
 // every respect but the dense products of its frame stages and vocoder (three fp16 MFMAs on split operands)
 bool is16(const Handle* h) { return h->cfg.precision == TTS_COMPUTE_BF16 || h->cfg.precision == TTS_COMPUTE_F16; }
 int bits16(const Handle* h) { return is16(h) ? 16 : 32; }
-// the PostFlow runs the stand-alone cond convs (fp32 / f32x3 handles, TOUCAN_NO_FUSED_WAVENET) and needs their output buffer
-bool postflow_cond_buffer(const Handle* h) { return !is16(h) || h->no_fused_wavenet; }
+// the PostFlow runs the stand-alone cond convs (fp32 / f32x3 handles) and needs their output buffer
+bool postflow_cond_buffer(const Handle* h) { return !is16(h); }
 
 // relative position tables of both stacks for positions -(pmax-1) .. pmax-1 (Attention.py:177, PositionalEncoding.py:90-130):
 // ptab[s][l][pmax - 1 + p] = linear_pos_l(pe(p)); the sinusoid table "pe" is uploaded by the host (fp32, built like the reference)
@@ -700,7 +697,7 @@ int conformer(Handle* h, int stack, float* x, const Layout& l, Arena& a, hipStre
     // Macaron feed-forward (EncoderLayer.py:84-90)
     // (the same decision as engine.py: 16-bit configuration and packed weights loaded - not the number of rows: an utterance's
     // result must not depend on the batch it is in)
-    const bool fuse_ffn = b16 == 16 && !h->no_fused_ffn;
+    const bool fuse_ffn = b16 == 16;
     if (fuse_ffn && b.ffm_fused) {
       TTS_TRY(ffn_fused(h, b.ffm_fused, b.ffm1, b.ffm2, b.ln_g[0], b.ln_b[0], nullptr, nullptr, x, R, st));
     } else {
@@ -711,11 +708,11 @@ int conformer(Handle* h, int stack, float* x, const Layout& l, Arena& a, hipStre
     // relative-position self-attention (:93-116)
     TTS_TRY(tts_layernorm(x, ATT, ln, ATT, b.ln_g[1], b.ln_b[1], R, ATT, 1e-12f, st));
     TTS_TRY(conv(h, b.qkv, T2(ln, ATT), T2(qkv, 3 * ATT), l, st));
-    if (b16 == 16 && !h->no_f16_attention)  // (16-bit configurations: the contractions on the fp16 matrix cores)
+    if (b16 == 16)  // (16-bit configurations: the contractions on the fp16 matrix cores)
       TTS_TRY(tts_relpos_attention_f16(qkv, 3 * ATT, h->ptab[stack] + bi * prow, h->pmax, b.u, b.v, ctx, ATT, HEADS, DK, t128.dev, t128.n, 128, st));
     else
       TTS_TRY(tts_relpos_attention(qkv, 3 * ATT, h->ptab[stack] + bi * prow, h->pmax, b.u, b.v, ctx, ATT, HEADS, DK, t128.dev, t128.n, 128,
-                                   b16 == 16 ? 0 : (h->split_mode == 2 ? TTS_ATT_KEY_SPLIT_ALWAYS : (h->split_mode == 1 ? TTS_ATT_KEY_SPLIT : 0)), st));
+                                   h->split_mode == 2 ? TTS_ATT_KEY_SPLIT_ALWAYS : (h->split_mode == 1 ? TTS_ATT_KEY_SPLIT : 0), st));
     TTS_TRY(conv(h, b.out, T2(ctx, ATT), T2(x, ATT), l, st, res1));
     // convolution module (:119-125, Convolution.py:31-55)
     TTS_TRY(tts_layernorm(x, ATT, ln, ATT, b.ln_g[2], b.ln_b[2], R, ATT, 1e-12f, st));
@@ -802,9 +799,6 @@ int pipeline_create(const TtsConfig* cfg, Handle** out) {
   Handle* h = new Handle();
   h->cfg = *cfg;
   if (cfg->small_tile_blocks > 0) h->small_tile_blocks = cfg->small_tile_blocks;
-  h->no_fused_wavenet = getenv("TOUCAN_NO_FUSED_WAVENET") != nullptr;
-  h->no_fused_ffn = getenv("TOUCAN_NO_FUSED_FFN") != nullptr;
-  h->no_f16_attention = getenv("TOUCAN_NO_F16_ATTENTION") != nullptr;
   *out = h;
   return TTS_OK;
 }

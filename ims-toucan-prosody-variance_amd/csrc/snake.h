@@ -73,8 +73,9 @@ __device__ __forceinline__ void snake_rows_fn(LoadFn load, int T, int t0, const 
 // pays the (26 samples / 8 frames) halo overhead of snake_rows_fn; with NCH = 5 the up-sampler + sine work per frame drops
 // from 3.25 to 2.25 samples.  store(i, v) receives frame t0+i (callers mask frames outside [0, T)).  The 8 frames a chunk
 // adds are requested one chunk ahead (reads run up to 21 frames ahead of the stores), so their latency hides under the math.
-// PREFETCH = false keeps 8 registers free (the 80-register C = 32 residual step is faster without it).
-template <int NCH, bool PREFETCH = true, class LoadFn, class StoreFn>
+// The prefetch costs 8 registers; every caller takes it, the C = 32 residual step included (two spill-free workgroups per CU
+// with it beat three without it by ~10 %, see resblock.hip).
+template <int NCH, class LoadFn, class StoreFn>
 __device__ __forceinline__ void snake_stream(LoadFn load, StoreFn store, int T, int t0, const float (&f)[12], float ea, float inv_b) {
   // The factor 2 of the zero-stuffed interpolation is carried as a scale: h = u/2 and s/2 = h + (1/2b) sin^2(2h e^alpha) are
   // what the registers hold, and the 12-tap decimator output is doubled once per frame (one multiply per frame instead of
@@ -97,17 +98,9 @@ __device__ __forceinline__ void snake_stream(LoadFn load, StoreFn store, int T, 
 #pragma unroll
       for (int i = 0; i < 12; ++i) xin[i] = xin[i + 8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        if constexpr (PREFETCH) {
-          xin[12 + i] = nxt[i];
-        } else {
-          int q = tc + 6 + i;
-          q = q < 0 ? 0 : (q > T - 1 ? T - 1 : q);
-          xin[12 + i] = load(q);
-        }
-      }
+      for (int i = 0; i < 8; ++i) xin[12 + i] = nxt[i];
     }
-    if (PREFETCH && c + 1 < NCH) {
+    if (c + 1 < NCH) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         int q = tc + 14 + i;

@@ -64,28 +64,25 @@ __global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc
   const int cb0 = n2 == 384 ? 3 * wave : P0, cb1 = n2 == 384 ? 3 * wave + 1 : P1, cb2 = n2 == 384 ? 3 * wave + 2 : P1;
 
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define WN_GLOAD128(dst_, ptr_) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst_) : "v"(ptr_) : "memory")
-#define WN_WAIT_VM(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
-#define WN_PIN(r_) asm volatile("" : "+v"(r_))
-  // The weight stream (see gemm_rows_kernel in conv1d.hip for the idiom): inline-asm loads the compiler does not count, WN_DEPTH
+  // The weight stream (see TTS_GLOAD128 in common.h for the idiom): inline-asm loads the compiler does not count, WN_DEPTH
   // k-steps ahead; they return in order, so before a k-step is consumed (WN_DEPTH - 1) * WN_L younger loads may stay in flight.
   // One stream runs through all products: the last block of a product requests the first k-steps of the next one.
   u32x4 wr[WN_DEPTH][WN_L];
   const char *q0, *q1, *q2, *q3;  // this lane's four fragment addresses of the next k-step to request
   size_t qs;                      // bytes per k-step
   auto request = [&](int slot) __attribute__((always_inline)) {
-    WN_GLOAD128(wr[slot][0], q0);
-    WN_GLOAD128(wr[slot][1], q1);
-    WN_GLOAD128(wr[slot][2], q2);
-    WN_GLOAD128(wr[slot][3], q3);
+    TTS_GLOAD128(wr[slot][0], q0);
+    TTS_GLOAD128(wr[slot][1], q1);
+    TTS_GLOAD128(wr[slot][2], q2);
+    TTS_GLOAD128(wr[slot][3], q3);
     q0 += qs; q1 += qs; q2 += qs; q3 += qs;
   };
   auto arrive = [&](int slot) __attribute__((always_inline)) {
-    WN_WAIT_VM((WN_DEPTH - 1) * WN_L);
-    WN_PIN(wr[slot][0]);
-    WN_PIN(wr[slot][1]);
-    WN_PIN(wr[slot][2]);
-    WN_PIN(wr[slot][3]);
+    TTS_WAIT_VM((WN_DEPTH - 1) * WN_L);
+    TTS_PIN(wr[slot][0]);
+    TTS_PIN(wr[slot][1]);
+    TTS_PIN(wr[slot][2]);
+    TTS_PIN(wr[slot][3]);
   };
   // packed [tap][k/8][n][8]: the A fragment of k-step s, column block cb = 16 bytes at ((2 s + lk) n + 32 cb + lrow) * 16
   auto stream_pairs = [&](const void* w, int n, int col0) __attribute__((always_inline)) {  // columns a | g of P0 and of P1
@@ -296,13 +293,13 @@ __global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc
       request(u);
     }
   }
-  WN_WAIT_VM(0);  // drain the tail requests: their destination registers stay allocated (pinned) until here
+  TTS_WAIT_VM(0);  // drain the tail requests: their destination registers stay allocated (pinned) until here
 #pragma unroll
   for (int u = 0; u < WN_DEPTH; ++u) {
-    WN_PIN(wr[u][0]);
-    WN_PIN(wr[u][1]);
-    WN_PIN(wr[u][2]);
-    WN_PIN(wr[u][3]);
+    TTS_PIN(wr[u][0]);
+    TTS_PIN(wr[u][1]);
+    TTS_PIN(wr[u][2]);
+    TTS_PIN(wr[u][3]);
   }
   // ---- [h | skip] out = in + res_skip + bias (last layer: the skip half only)
   {
@@ -328,9 +325,6 @@ __global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc
       store_block(acc[5], cb2, fQ);
     }
   }
-#undef WN_GLOAD128
-#undef WN_WAIT_VM
-#undef WN_PIN
 }
 
 namespace {

@@ -8,7 +8,6 @@ Layout: activations are time-major [rows, channels], all utterances of the batch
 (ragged.py).  The reference mirrors are cited per method.
 """
 import ctypes as C
-import os
 import math
 
 import numpy as np
@@ -79,7 +78,7 @@ class Ops:
         # convs / key-split attention at every grid size (phoneme stages: everything upstream of the rounded durations keeps one
         # arithmetic whatever the batch), 1 = on small grids only (frame stages), 0 = never (vocoder: chunked == whole)
         self.split_k = 0
-        self.small_tile_blocks = int(os.environ.get("TOUCAN_SMALL_TILE_BLOCKS", "1536"))  # regular conv grids below this many workgroups switch to the 64 x 64 small-batch form (0: never)
+        self.small_tile_blocks = 1536  # regular conv grids below this many workgroups switch to the 64 x 64 small-batch form (0: never)
         self._fir_tabs = {}
         self.default_compute = COMPUTE_F32  # convs whose weights carry a 16-bit copy run on bf16 / fp16 MFMA when this is not COMPUTE_F32
 
@@ -352,9 +351,6 @@ class GraphCache:
         return outs
 
 
-NO_F16_ATTENTION = bool(os.environ.get("TOUCAN_NO_F16_ATTENTION"))  # (A/B switch, csrc/pipeline.hip reads the same variable)
-
-
 class ConformerWeights:
     """Packed weights of one Layers/Conformer.py stack (6 EncoderLayers)."""
 
@@ -372,7 +368,7 @@ class ConformerWeights:
                 blk[ff + ".w2"] = pack(sd[p + ff + ".w_2.weight"], sd[p + ff + ".w_2.bias"], device)
                 # 16-bit configurations, kernel size 1: the whole module is one launch (tts_ffn_fused) on weights in its fragment order
                 w1 = np.asarray(sd[p + ff + ".w_1.weight"])
-                if bf16 in ("bf16", "f16", True) and not os.environ.get("TOUCAN_NO_FUSED_FFN") and (w1.ndim == 2 or w1.shape[2] == 1) and w1.shape[1] == ATT and w1.shape[0] % 32 == 0:
+                if bf16 in ("bf16", "f16", True) and (w1.ndim == 2 or w1.shape[2] == 1) and w1.shape[1] == ATT and w1.shape[0] % 32 == 0:
                     blk[ff + ".fused"] = packing.pack_ffn(w1, sd[p + ff + ".w_1.bias"], sd[p + ff + ".w_2.weight"], device, "f16" if bf16 == "f16" else "bf16")
             a = p + "self_attn."
             wqkv = np.concatenate([sd[a + f"linear_{n}.weight"] for n in "qkv"], axis=0)
@@ -532,7 +528,7 @@ class AcousticEngine:
                 ops.conv(blk["feed_forward_macaron.w2"], hid, x, rag, alpha=0.5, res=x)
             ops.layernorm(x, ln, *blk["norm_mha"], R, ATT)
             ops.conv(blk["qkv"], ln, qkv, rag)
-            ops.attention(qkv, cw.ptabs[li], cw.pmax, blk["u"], blk["v"], ctx, rag, f16=self.bf16 and not NO_F16_ATTENTION)
+            ops.attention(qkv, cw.ptabs[li], cw.pmax, blk["u"], blk["v"], ctx, rag, f16=self.bf16)
             ops.conv(blk["out"], ctx, x, rag, res=x)
             ops.layernorm(x, ln, *blk["norm_conv"], R, ATT)
             ops.conv(blk["pw1"], ln, glu, rag)
@@ -756,7 +752,7 @@ class AcousticEngine:
         x.copy_(z_sq)
         hs = ops.empty(RS, 2 * ATT)  # [hidden state | skip sum] side by side: one accumulating conv per WaveNet layer updates both
         # 16-bit configurations: one launch per WaveNet layer (tts_wavenet_layer), the state ping-pongs between two buffers
-        fused = self.bf16 and os.environ.get("TOUCAN_NO_FUSED_WAVENET") is None
+        fused = self.bf16
         hs2 = ops.empty(RS, 2 * ATT) if fused else None
         h, skip = hs[:, :ATT], hs[:, ATT:]
         acts = ops.empty(RS, ATT, dtype=self.dt16)  # read only by the res/skip conv (16-bit MFMA)

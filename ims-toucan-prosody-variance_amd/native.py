@@ -6,7 +6,6 @@ This is the product path of ``ToucanTTSInterface`` on a GPU.  The Python-sequenc
 tests, for HIP-graph capture and for the CPU host-logic tests that drive the numpy ABI emulator.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -52,7 +51,7 @@ class NativePipeline:
             voc = engine.VocoderEngine(vocoder_sd, vocoder_kind, "cpu", precision=self.vocoder_precision, pack_only=True)
         kind_code = {None: 0, "hifigan": 1, "bigvgan": 2}[vocoder_kind]
         post_b = float(voc.post_b) if voc is not None else 0.0
-        stb = int(os.environ.get("TOUCAN_SMALL_TILE_BLOCKS", "0"))  # same A/B switch as engine.Ops (0: the library's default, 1536)
+        stb = 0  # small_tile_blocks: the library's default, 1536
         cfg = capi.TtsConfig(int(self.multilingual), int(self.multispeaker), 0 if split else kind_code, compute, stb, post_b)
         self.h = C.c_void_p()
         self.h_voc = self.h  # the handle the vocoder entries are called on (its own when the precisions differ)

@@ -1,5 +1,5 @@
 """Spread of the launch time of tts_resblock_step over 200 back-to-back launches per shape (run on the MI355X box): median, p99,
-maximum, outliers - the persistent work-queue kernel must not have any (TOUCAN_RB_WG_PER_CU=-1: one workgroup per tile)."""
+maximum, outliers - the persistent work-queue kernel must not have any."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
