@@ -14,7 +14,10 @@ for a ragged batch of recordings:
 fp32 throughout and no precision switch: durations are integers taken from an argmax path.  Every launch computes an utterance in
 an order that depends on that utterance alone, so a batch returns bit for bit what its utterances return one by one.
 
-Not reproduced: grapheme-to-phoneme conversion (the transcript is a phoneme string), the on-line CTC fine-tuning,
+The reference's on-line fine-tuning of the aligner on the utterance (five SGD steps of CTC training) is opt-in: ``fine_tune=`` runs
+it per utterance on the kernels of csrc/train.hip (finetune.py) and aligns on the fine-tuned logits.
+
+Not reproduced: grapheme-to-phoneme conversion (the transcript is a phoneme string),
 and the silero voice-activity trim (``speech_bounds`` gives the speech span instead).  Praat itself is not reproduced bit for bit:
 ``f0="track"`` runs a restatement of its published algorithm (pitch.py).
 """
@@ -267,6 +270,7 @@ class ProsodyExtractor:
 
     def __init__(self, aligner_state_dict, device, timing=False):
         self.aligner = AlignerEngine(aligner_state_dict, device, timing=timing)
+        self._state_dict, self._tuner = aligner_state_dict, None  # finetune.AlignerFineTuner, built when first asked for
         self.ops = self.aligner.ops
         self.device = self.aligner.device
         self.logmel = style.LogMel(self.device)
@@ -330,13 +334,35 @@ class ProsodyExtractor:
                                              ops.stream()), "tts_token_average")
         return out
 
+    def fine_tuned_logits(self, x, rag, ids, fine_tune):
+        """Per utterance: five SGD steps on a copy of the checkpoint's weights, then the eval-mode logits (finetune.py).  fine_tune:
+        per utterance a seed for ``finetune.dropout_masks`` or explicit masks [steps][5] of [T, 512]."""
+        from . import finetune
+        if len(fine_tune) != rag.n_seq:
+            raise ValueError(f"{len(fine_tune)} fine-tuning seeds / mask sets for {rag.n_seq} utterances")
+        if self._tuner is None:
+            self._tuner = finetune.AlignerFineTuner(self._state_dict, self.device, lib=self.ops.lib)
+        lg = torch.zeros(x.shape[0], N_SYMBOLS, dtype=torch.float32, device=self.device)
+        self.last_fine_tune = []
+        for b, (b0, n) in enumerate(zip(rag.begins, rag.lengths)):
+            ft = fine_tune[b]
+            masks = finetune.dropout_masks(ft, n) if isinstance(ft, (int, np.integer)) else ft
+            lg[b0:b0 + n] = self._tuner.fine_tune(x[b0:b0 + n], ids[b], masks)
+            self.last_fine_tune.append((self._tuner.last_loss, self._tuner.last_norm))
+        return lg
+
     @torch.inference_mode()
-    def extract(self, feats, waves16, f0=None, mels=None):
+    def extract(self, feats, waves16, f0=None, mels=None, fine_tune=None):
         """feats: [L_b, 62] per utterance; waves16: speech spans at 16 kHz.  f0: None, frame-level tracks (Hz, 0 = unvoiced), or
         "track" - for every utterance or as an entry of the list - to compute them on the device.  mels: optional log-mels to align
-        on instead of the ones computed here (the golden test feeds the reference's).
+        on instead of the ones computed here (the golden test feeds the reference's).  fine_tune: None, or per utterance a seed
+        or explicit dropout masks: the aligner is fine-tuned on each utterance before it aligns it (``fine_tuned_logits``).
         -> list of (durations, pitch or None, energy) CPU tensors."""
         ops, al = self.ops, self.aligner
+        if fine_tune is not None:  # before the front end, which asserts on a span shorter than half its window
+            from . import finetune
+            for b, w in enumerate(waves16):
+                finetune.check_frames(1 + np.asarray(w).size // style.HOP, f"utterance {b}")  # the frame count of ``spectra``
         f0 = self.tracked_f0(waves16, f0)
         spec, rag = self.spectra(waves16)
         if mels is None:
@@ -350,7 +376,7 @@ class ProsodyExtractor:
             x = torch.from_numpy(xh).to(self.device)  # one upload
         tok = [token_ids(f) for f in feats]
         ids, flags = [t[0] for t in tok], [t[1] for t in tok]
-        lg = al.logits(x, rag)
+        lg = al.logits(x, rag) if fine_tune is None else self.fine_tuned_logits(x, rag, ids, fine_tune)
         al._mark("mas")
         dur, full_begin = al.durations(lg, rag, ids, flags)
         al._mark("energy")
@@ -369,7 +395,7 @@ class ProsodyExtractor:
             pitch = self.token_average(torch.from_numpy(track).to(self.device), rag, dur, keep_p, full_begin, n_full, 1)
         al._mark("end")
         al._collect()
-        self.last_logits, self.last_rag = lg, rag
+        self.last_logits, self.last_rag, self.last_mel = lg, rag, x
         dur, energy = dur.cpu(), energy.cpu()
         pitch = pitch.cpu() if pitch is not None else None
         out = []
@@ -378,12 +404,13 @@ class ProsodyExtractor:
         return out
 
 
-def extract_prosody_batch(extractor, phone_strings, waves, sr, f0=None, speech_bounds=None):
+def extract_prosody_batch(extractor, phone_strings, waves, sr, f0=None, speech_bounds=None, fine_tune=None):
     """Per utterance (durations, pitch or None, energy, start_silence, end_silence), as UtteranceCloner.extract_prosody returns them.
     waves: recordings at `sr` (a list, or one array per utterance); f0: optional frame-level tracks (Hz, 0 = unvoiced, hop 256 at
     16 kHz), or "track" (for all, or in place of an utterance's track) to compute them on the device from the speech span;
     speech_bounds: optional (start, end) sample indices of the speech in the normalised 16 kHz wave - the silero trim's
-    result - else the whole wave is speech and both silences are 0."""
+    result - else the whole wave is speech and both silences are 0; fine_tune: None, or per utterance a seed or explicit dropout masks
+    for the on-line fine-tuning of the aligner (ProsodyExtractor.extract)."""
     srs = sr if isinstance(sr, (list, tuple)) else [sr] * len(waves)
     feats, spans, sil = [], [], []
     for b, (ph, w, r) in enumerate(zip(phone_strings, waves, srs)):
@@ -392,5 +419,5 @@ def extract_prosody_batch(extractor, phone_strings, waves, sr, f0=None, speech_b
         s, e = (0, len(norm)) if speech_bounds is None or speech_bounds[b] is None else (int(speech_bounds[b][0]), int(speech_bounds[b][1]))
         spans.append(norm[s:e])
         sil.append((s, len(norm) - e))
-    res = extractor.extract(feats, spans, f0=f0)
+    res = extractor.extract(feats, spans, f0=f0, fine_tune=fine_tune)
     return [(d, p, en, s0, s1) for (d, p, en), (s0, s1) in zip(res, sil)]

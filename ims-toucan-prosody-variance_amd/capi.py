@@ -205,6 +205,23 @@ PITCH_PROTOTYPES = {
 PITCH_CANDIDATES, PITCH_LAGS, PITCH_WINDOW = 15, 600, 1198  # include/toucan_pitch.h TTS_PITCH_CANDIDATES, _LAGS, _WINDOW
 PITCH_MIN_SAMPLES, PITCH_PATH_LDS_FRAMES = 1200, 2048  # TTS_PITCH_MIN_SAMPLES, TTS_PITCH_PATH_LDS_FRAMES
 
+# symbol -> (restype, argtypes); mirrors include/toucan_train.h (the aligner's on-line fine-tuning: csrc/train.hip) one to one
+_l = C.c_int64
+TRAIN_PROTOTYPES = {
+    "tts_gemm_f32": (C.c_int, [_i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
+    "tts_bn_train_forward": (C.c_int, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _f, _f, _p]),
+    "tts_bn_train_backward": (C.c_int, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p]),
+    "tts_bn_eval_affine": (C.c_int, [_p, _p, _p, _p, _p, _p, _i, _f, _p]),
+    "tts_lstm_train_step": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p]),
+    "tts_lstm_backward_step": (C.c_int, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "tts_ctc_grad": (C.c_int, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _i, _p]),
+    "tts_col_sum": (C.c_int, [_p, _i, _i, _i, _p, _p, _p]),
+    "tts_sumsq": (C.c_int, [_p, _l, _p, _p, _p]),
+    "tts_sgd_clip_update": (C.c_int, [_p, _p, _l, _p, _f, _f, _p]),
+}
+GEMM_NN, GEMM_NT, GEMM_TN = 0, 1, 2  # include/toucan_train.h TTS_GEMM_*
+CTC_GRAD_MAX_TARGETS, SUMSQ_PARTIALS = 768, 256  # TTS_CTC_GRAD_MAX_TARGETS, TTS_SUMSQ_PARTIALS
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -228,7 +245,7 @@ def lib():
     handle = C.CDLL(LIB_PATH)
     _assert_single_hip_runtime()
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
-            list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()):
+            list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -1,9 +1,11 @@
 """Drop-in counterpart of InferenceInterfaces/UtteranceCloner.py (:19-194) on the HIP engines: the reference's constructor and
 methods, with the prosody extracted on the GPU (align.py) for one recording or a ragged batch of them.
 
-Stated deviations: the transcript is a phoneme string (no G2P offline); ``on_line_fine_tune=True`` is accepted
-with a one-time warning and not performed (the reference's five SGD steps of CTC training), so the result is that of the
-eval-mode aligner; there is no silero voice-activity trim (the silences are 0 unless ``speech_bounds`` gives the speech span);
+Stated deviations: the transcript is a phoneme string (no G2P offline); by default ``on_line_fine_tune=True`` is
+accepted with a one-time warning and not performed (the reference's five SGD steps of CTC training), so the result is that of the
+eval-mode aligner - an instance made with ``fine_tune_aligner=True`` performs it on the GPU (finetune.py), per utterance from the
+checkpoint's weights, with dropout masks drawn from ``torch.Generator(fine_tune_seed)`` as the reference draws them on a CPU device
+(or given as ``dropout_masks=``); there is no silero voice-activity trim (the silences are 0 unless ``speech_bounds`` gives the speech span);
 pitch comes from ``f0=``: a frame-level track, or ``"track"`` for the device pitch tracker (pitch.py: Praat's autocorrelation
 method restated from its publication, parity with Praat unpinned and therefore opt-in; ``track_pitch=True`` makes it the default of
 this instance); with neither, pitch is None and the acoustic model predicts it from the cloned durations.
@@ -21,11 +23,14 @@ from .interface import ToucanTTSInterface, write_wav
 class UtteranceCloner:
     _warned_fine_tune = False
 
-    def __init__(self, model_id, device, language="en", speed_over_quality=False, track_pitch=False):
+    def __init__(self, model_id, device, language="en", speed_over_quality=False, track_pitch=False, fine_tune_aligner=False,
+                 fine_tune_seed=0):
         self.tts = ToucanTTSInterface(device=device, tts_model_path=model_id, faster_vocoder=speed_over_quality, language=language)
         self.device = device
         self.language = language
         self.track_pitch = track_pitch  # additive: methods called without f0= behave as f0="track"
+        self.fine_tune_aligner = fine_tune_aligner  # additive: on_line_fine_tune=True is performed instead of warned about
+        self.fine_tune_seed = fine_tune_seed  # every utterance's dropout masks start from this seed
         path = os.path.join(interface.MODELS_DIR, "Aligner", "aligner.pt")
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path}: aligner checkpoint not found (offline, write the fixture one with "
@@ -39,20 +44,32 @@ class UtteranceCloner:
             warnings.warn("on_line_fine_tune=True: the aligner's on-line CTC fine-tuning is not performed; the durations are those of "
                           "the aligner as loaded (the reference's on_line_fine_tune=False, in eval mode)", stacklevel=3)
 
-    def extract_prosody_batch(self, transcripts, waves, sr, f0=None, speech_bounds=None, on_line_fine_tune=True):
-        """Per utterance (durations, pitch or None, energy, start_silence, end_silence) for phoneme transcripts and recordings at `sr`."""
-        self._fine_tune_notice(on_line_fine_tune)
+    def extract_prosody_batch(self, transcripts, waves, sr, f0=None, speech_bounds=None, on_line_fine_tune=True, dropout_masks=None):
+        """Per utterance (durations, pitch or None, energy, start_silence, end_silence) for phoneme transcripts and recordings at `sr`.
+        dropout_masks (fine_tune_aligner instances): per utterance [5 steps][5 layers] boolean [T, 512] keep-masks in place of the
+        ones drawn from fine_tune_seed."""
+        fine_tune = None
+        if dropout_masks is not None and not (self.fine_tune_aligner and on_line_fine_tune):
+            raise ValueError("dropout_masks= needs fine_tune_aligner=True and on_line_fine_tune=True")
+        if self.fine_tune_aligner:
+            if on_line_fine_tune:
+                fine_tune = [self.fine_tune_seed] * len(waves) if dropout_masks is None else list(dropout_masks)
+        else:
+            self._fine_tune_notice(on_line_fine_tune)
         if f0 is None and self.track_pitch:
             f0 = pitch.TRACK
-        return align.extract_prosody_batch(self.extractor, transcripts, waves, sr, f0=f0, speech_bounds=speech_bounds)
+        return align.extract_prosody_batch(self.extractor, transcripts, waves, sr, f0=f0, speech_bounds=speech_bounds, fine_tune=fine_tune)
 
-    def extract_prosody(self, transcript, ref_audio_path, lang="de", on_line_fine_tune=True, f0=None, speech_bounds=None):
+    def extract_prosody(self, transcript, ref_audio_path, lang="de", on_line_fine_tune=True, f0=None, speech_bounds=None, dropout_masks=None):
         """UtteranceCloner.py:46-145: (duration, pitch, energy, start_silence, end_silence) for one recording.  `lang` only selects
         the phonemizer in the reference; the transcript here is already phonemes."""
-        self._fine_tune_notice(on_line_fine_tune)
+        if not self.fine_tune_aligner:
+            self._fine_tune_notice(on_line_fine_tune)
         wave, sr = style.read_audio(ref_audio_path)
         return self.extract_prosody_batch([transcript], [wave], sr, f0=None if f0 is None else [f0],  # [f0]: an array or "track"
-                                          speech_bounds=None if speech_bounds is None else [speech_bounds], on_line_fine_tune=False)[0]
+                                          speech_bounds=None if speech_bounds is None else [speech_bounds],
+                                          on_line_fine_tune=on_line_fine_tune and self.fine_tune_aligner,
+                                          dropout_masks=None if dropout_masks is None else [dropout_masks])[0]
 
     def clone_utterance(self, path_to_reference_audio_for_intonation, path_to_reference_audio_for_voice, transcription_of_intonation_reference,
                         filename_of_result=None, lang="de", f0=None, speech_bounds=None, z_noise=None):
