@@ -222,6 +222,18 @@ TRAIN_PROTOTYPES = {
 GEMM_NN, GEMM_NT, GEMM_TN = 0, 1, 2  # include/toucan_train.h TTS_GEMM_*
 CTC_GRAD_MAX_TARGETS, SUMSQ_PARTIALS = 768, 256  # TTS_CTC_GRAD_MAX_TARGETS, TTS_SUMSQ_PARTIALS
 
+
+class TtsResampleSpan(C.Structure):
+    _fields_ = [("in_begin", _l), ("n_held", _l), ("pos0", _l), ("out_first", _l), ("out_count", _l), ("out_begin", _l)]
+
+
+# symbol -> (restype, argtypes); mirrors include/toucan_resample.h (the sample-rate converter: csrc/resample.hip) one to one
+RESAMPLE_PROTOTYPES = {
+    "tts_resample_tile_outputs": (C.c_int, []),
+    "tts_resample": (C.c_int, [_p, _p, _p, _i, _l, _i, _i, _i, _i, _p, _p]),
+}
+RESAMPLE_MAX_FACTOR, RESAMPLE_LDS_TABLE_BYTES = 1024, 65536  # include/toucan_resample.h TTS_RESAMPLE_MAX_FACTOR, _LDS_TABLE_BYTES
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -245,7 +257,7 @@ def lib():
     handle = C.CDLL(LIB_PATH)
     _assert_single_hip_runtime()
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
-            list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()):
+            list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -205,27 +205,34 @@ class ToucanTTSInterface(torch.nn.Module):
                 energy=None,
                 input_is_phones=False,
                 return_plot_as_filepath=False,
-                z_noise=None):
-        """The reference's signature (ToucanTTSInterface.py:132-143) plus one additive keyword: ``z_noise`` [80, T] - the PostFlow
-        noise 0.8 N(0,1) the reference draws inside the model (Glow.py:363) - so that a call can be reproduced and checked
-        against the oracle; None draws it on the device."""
+                z_noise=None,
+                sample_rate=None,
+                pcm16=False):
+        """The reference's signature (ToucanTTSInterface.py:132-143) plus additive keywords.  ``z_noise`` [80, T]: the PostFlow
+        noise 0.8 N(0,1) the reference draws inside the model (Glow.py:363), so that a call can be reproduced and checked
+        against the oracle; None draws it on the device.  ``sample_rate`` / ``pcm16``: the waveform at another rate than 24 kHz
+        and / or as int16, converted on the device (resample.py); the figure of ``view`` keeps drawing the 24 kHz wave."""
+        self._check_output_format(sample_rate, pcm16)
         with torch.inference_mode():
             phones = self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
-            wavs = self._synthesize([phones], [self.default_utterance_embedding], [self._lang()],
-                                    z_noise=None if z_noise is None else [z_noise],
-                                    durations=None if durations is None else [durations],
-                                    pitch=None if pitch is None else [pitch],
-                                    energy=None if energy is None else [energy],
-                                    duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
-                                    energy_variance_scale=energy_variance_scale,
-                                    pause_duration_scaling_factor=pause_duration_scaling_factor)
+            wav24, spans = self._synthesize_packed([phones], [self.default_utterance_embedding], [self._lang()],
+                                                   z_noise=None if z_noise is None else [z_noise],
+                                                   durations=None if durations is None else [durations],
+                                                   pitch=None if pitch is None else [pitch],
+                                                   energy=None if energy is None else [energy],
+                                                   duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
+                                                   energy_variance_scale=energy_variance_scale,
+                                                   pause_duration_scaling_factor=pause_duration_scaling_factor)
+            wav, out_spans = self._convert(wav24, spans, sample_rate, pcm16)
+            wavs = [wav[b:b + n] for b, n in out_spans]
         if view or return_plot_as_filepath:  # ToucanTTSInterface.py:171-226 (matplotlib only: plotting.py)
             from . import plotting
             if input_is_phones:
                 labels = text.replace(" ", "|")
             else:
                 labels = self.text2phone.get_phone_string(text, for_plot_labels=True)
-            fig = plotting.draw(wavs[0].cpu().numpy(), self.last_mel[0].cpu().numpy(), self.last_durations[0].cpu().numpy(),
+            b24, n24 = spans[0]
+            fig = plotting.draw(wav24[b24:b24 + n24].cpu().numpy(), self.last_mel[0].cpu().numpy(), self.last_durations[0].cpu().numpy(),
                                 self.last_pitch[0].cpu().numpy(), labels, text)
             if return_plot_as_filepath:
                 return wavs[0], plotting.show_or_save(fig, "tmp.png")
@@ -247,9 +254,34 @@ class ToucanTTSInterface(torch.nn.Module):
         self.last_mel = out["mel"]
         return wav, list(zip(rag.begins, rag.lengths))
 
-    def _synthesize(self, phones, embs, langs, z_noise=None, **kw):
+    def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, **kw):
         wav, spans = self._synthesize_packed(phones, embs, langs, z_noise=z_noise, **kw)
+        wav, spans = self._convert(wav, spans, sample_rate, pcm16)
         return [wav[b:b + n] for b, n in spans]
+
+    SAMPLE_RATE = 24000  # what both vocoders generate
+
+    @staticmethod
+    def _check_output_format(sample_rate, pcm16):
+        """ValueError for a rate the resampler cannot serve; True if the 24 kHz float32 waveform has to be converted at all."""
+        if sample_rate is None or sample_rate == ToucanTTSInterface.SAMPLE_RATE:
+            return bool(pcm16)
+        from . import resample
+        resample.ratio(ToucanTTSInterface.SAMPLE_RATE, sample_rate)
+        return True
+
+    def _resampler(self):
+        if getattr(self, "_resampler_obj", None) is None:
+            from . import resample
+            self._resampler_obj = resample.Resampler(self.device)
+        return self._resampler_obj
+
+    def _convert(self, wav, spans, sample_rate, pcm16):
+        """The packed 24 kHz waveform and its spans at ``sample_rate`` (None: 24 kHz), as int16 with ``pcm16``, every utterance
+        converted on its own on the device, behind the vocoder on its stream.  24 kHz float32 is returned as it came."""
+        if not self._check_output_format(sample_rate, pcm16):
+            return wav, spans
+        return self._resampler().resample(wav.contiguous(), spans, self.SAMPLE_RATE, sample_rate or self.SAMPLE_RATE, pcm16)
 
     def predict_frame_counts(self, feats, embs, pitch=None, energy=None, **kw):
         """Mel frames each utterance will get (stage A only) - the balancing key of the multi-GPU deal."""
@@ -259,12 +291,16 @@ class ToucanTTSInterface(torch.nn.Module):
 
     def synthesize_batch(self, texts, input_is_phones=True, utterance_embeddings=None, z_noise=None, durations=None, pitch=None,
                          energy=None, duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
-                         pause_duration_scaling_factor=1.0, distributed=False):
+                         pause_duration_scaling_factor=1.0, distributed=False, sample_rate=None, pcm16=False):
         """Additive API: a ragged batch in one pass; each utterance equals the reference run on it alone (16-bit configurations: bit
         for bit whatever the batch; fp32: durations / pitch / energy bit for bit, the mel to fp32 rounding order - DESIGN.md section 4).
         texts: phoneme strings (or [L,62] feature tensors).  durations / pitch / energy: optional per-utterance gold prosody (the
         cloner-style call, UtteranceCloner.py:163).  With ``distributed=True`` and an initialised process group the utterances are
-        dealt over the ranks by frame count and every rank returns all waveforms (distributed.py)."""
+        dealt over the ranks by frame count and every rank returns all waveforms (distributed.py).  ``sample_rate`` / ``pcm16``:
+        the waveforms at another rate than 24 kHz and / or as int16, converted on the device (not with ``distributed=True``)."""
+        if distributed and (sample_rate is not None or pcm16):
+            raise ValueError("sample_rate / pcm16 are not available with distributed=True: the sharded exchange carries 24 kHz float32")
+        self._check_output_format(sample_rate, pcm16)
         feats = [t if torch.is_tensor(t) else self.text2phone.string_to_tensor(t, input_phonemes=input_is_phones) for t in texts]
         embs = utterance_embeddings if utterance_embeddings is not None else [self.default_utterance_embedding] * len(feats)
         kw = dict(duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
@@ -272,27 +308,35 @@ class ToucanTTSInterface(torch.nn.Module):
         if not distributed:
             with torch.inference_mode():
                 return self._synthesize(feats, embs, [self._lang()] * len(feats), z_noise=z_noise, durations=durations, pitch=pitch,
-                                        energy=energy, **kw)
+                                        energy=energy, sample_rate=sample_rate, pcm16=pcm16, **kw)
         from . import distributed as dd
         return dd.synthesize_sharded(self, feats, embs, z_noise, durations, pitch, energy, kw)
 
-    def synthesize_ensemble(self, text, utterance_embeddings, durations=None, pitch=None, energy=None, input_is_phones=True, z_noise=None):
+    def synthesize_ensemble(self, text, utterance_embeddings, durations=None, pitch=None, energy=None, input_is_phones=True, z_noise=None,
+                            sample_rate=None, pcm16=False):
         """Several voices speaking one text with the same prosody, averaged (UtteranceCloner.py:166-194's ensemble) - as ONE batch
         over the voices instead of a loop that swaps the default embedding.  Without gold durations the voices may predict
-        different lengths; the mean is then taken over the common prefix."""
+        different lengths; the mean is then taken over the common prefix.  ``sample_rate`` / ``pcm16`` convert the 24 kHz mean."""
+        convert = self._check_output_format(sample_rate, pcm16)
         n = len(utterance_embeddings)
         rep = lambda v: None if v is None else [v] * n
         waves = self.synthesize_batch([text] * n, input_is_phones=input_is_phones, utterance_embeddings=list(utterance_embeddings),
                                       durations=rep(durations), pitch=rep(pitch), energy=rep(energy), z_noise=z_noise)
         m = min(w.numel() for w in waves)
-        return torch.stack([w[:m] for w in waves]).mean(dim=0)
+        mean = torch.stack([w[:m] for w in waves]).mean(dim=0)
+        if not convert:
+            return mean
+        wav, spans = self._convert(mean, [(0, m)], sample_rate, pcm16)
+        return wav[spans[0][0]:spans[0][0] + spans[0][1]]
 
-    def stream(self, text, input_is_phones=False, chunk_frames=512, halo_frames=None, max_batch=4, z_noise=None, **prosody):
+    def stream(self, text, input_is_phones=False, chunk_frames=512, halo_frames=None, max_batch=4, z_noise=None, sample_rate=None, pcm16=False, **prosody):
         """Generator of waveform pieces for ONE (long) text: the acoustic model runs once, the vocoder chunk-wise with overlap
         (streaming.py) - the concatenation equals ``self(text, ...)`` bit for bit, the first piece is ready after one chunk and the
         vocoder's workspace is bounded by ``max_batch`` chunks.  prosody: the keyword arguments of ``forward`` (gold durations /
-        pitch / energy, scaling factors)."""
+        pitch / energy, scaling factors).  ``sample_rate`` / ``pcm16``: the pieces at another rate and / or as int16, converted as
+        they come (resample.Resampler.streamer); their concatenation equals ``self(text, sample_rate=..., pcm16=...)`` bit for bit."""
         from . import streaming
+        convert = self._check_output_format(sample_rate, pcm16)
         halo = streaming.DEFAULT_HALO if halo_frames is None else halo_frames
         listed = {k: [v] for k, v in prosody.items() if k in ("durations", "pitch", "energy") and v is not None}
         scales = {k: v for k, v in prosody.items() if k.endswith("_factor") or k.endswith("_scale")}
@@ -307,7 +351,18 @@ class ToucanTTSInterface(torch.nn.Module):
                 out = self.phone2mel.forward([phones], emb, langs, z_noise=None if z_noise is None else [z_noise], **listed, **scales)
                 vocode = self.mel2wav.forward
             self.last_durations, self.last_pitch, self.last_energy = out["durations"], out["pitch"], out["energy"]
-            yield from streaming.stream_vocode(vocode, out["mel"][0].contiguous(), chunk_frames, halo, max_batch)
+            pieces = streaming.stream_vocode(vocode, out["mel"][0].contiguous(), chunk_frames, halo, max_batch)
+            if not convert:
+                yield from pieces
+                return
+            st = self._resampler().streamer(self.SAMPLE_RATE, sample_rate or self.SAMPLE_RATE, pcm16)
+            for piece in pieces:
+                done = st.push(piece)
+                if done.numel():
+                    yield done
+            done = st.finish()
+            if done.numel():
+                yield done
 
     SILENCE_SAMPLES = 10600   # between sentences in read_to_file (ToucanTTSInterface.py:267)
     MAX_FILE_BATCH = 32       # sentences synthesised per ragged batch by read_to_file
@@ -323,10 +378,19 @@ class ToucanTTSInterface(torch.nn.Module):
                      pitch_list=None,
                      energy_list=None,
                      increased_compatibility_mode=False,
-                     input_is_phones=False):
+                     input_is_phones=False,
+                     sample_rate=None,
+                     pcm16=False):
         """Same result as the reference's sentence loop (:231-285: silence, sentence, silence, ... with blank strings skipped,
         24 kHz float file or sample-doubled 48 kHz PCM16), but the sentences go through the engines as ragged batches of up to
-        MAX_FILE_BATCH utterances and the file is assembled once on the host."""
+        MAX_FILE_BATCH utterances and the file is assembled once on the host.  ``sample_rate`` / ``pcm16`` (additive): every
+        sentence is converted on the device on its own, the silence is ceil(10600 new / orig) samples and the file has that rate;
+        with ``pcm16`` the writer gets the device's int16.  Not with ``increased_compatibility_mode``, which stays the
+        reference's doubling."""
+        if increased_compatibility_mode and (sample_rate is not None or pcm16):
+            raise ValueError("increased_compatibility_mode is the reference's sample doubling to 48 kHz PCM16: it does not combine with "
+                             "sample_rate / pcm16")
+        self._check_output_format(sample_rate, pcm16)
         n = len(text_list)
         column = lambda lst: list(lst) + [None] * (n - len(lst)) if lst else [None] * n
         durs, pits, enes = column(dur_list), column(pitch_list), column(energy_list)
@@ -348,12 +412,16 @@ class ToucanTTSInterface(torch.nn.Module):
                                               pitch=[pits[i] for i in idx] if has_p else None,
                                               energy=[enes[i] for i in idx] if has_e else None,
                                               duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
-                                              energy_variance_scale=energy_variance_scale)
+                                              energy_variance_scale=energy_variance_scale, sample_rate=sample_rate, pcm16=pcm16)
                 for i, w in zip(idx, waves):
                     pieces[i] = w.cpu().numpy()
+        rate = self.SAMPLE_RATE if sample_rate is None else int(sample_rate)
         gap = self.SILENCE_SAMPLES
+        if rate != self.SAMPLE_RATE:
+            from . import resample
+            gap = resample.out_length(gap, self.SAMPLE_RATE, rate)
         total = gap + sum(pieces[i].shape[0] + gap for i in spoken)
-        audio = np.zeros(total, dtype=np.float32)
+        audio = np.zeros(total, dtype=np.int16 if pcm16 else np.float32)
         at = gap
         for i in spoken:
             audio[at:at + pieces[i].shape[0]] = pieces[i]
@@ -361,7 +429,7 @@ class ToucanTTSInterface(torch.nn.Module):
         if increased_compatibility_mode:  # 24 kHz is less widely supported than 48 kHz: every sample twice, 16-bit integers
             write_wav(file_location, float2pcm(np.repeat(audio, 2)), 48000)
         else:
-            write_wav(file_location, audio, 24000)
+            write_wav(file_location, audio, rate)
 
     def read_aloud(self, text, view=False, duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
                    blocking=False, increased_compatibility_mode=False):
