@@ -176,8 +176,13 @@ SCORE_PROTOTYPES = {
     "tts_score_losses": (C.c_int, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
     "tts_teacher_forced": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(_i), _p]),
     "tts_copy_decoder_mel": (C.c_int, [_p, _p, _i, _p]),
+    # the glow loss (csrc/glow_forward.hip, stage entry in csrc/pipeline.hip)
+    "tts_glow_forward_rows": (C.c_int, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
+    "tts_glow_nll_reduce": (C.c_int, [_p, _i, _p, _p, _p, _p, _i, C.c_double, _p, _p, _p]),
+    "tts_postflow_nll": (C.c_int, [_p, _p, _i, _p, _p, _p, _p]),
 }
 CTC_MAX_TARGETS = 2048  # include/toucan_score.h TTS_CTC_MAX_TARGETS
+GLOW_FORWARD_BLOCK_ROWS, GLOW_FORWARD_GRID_ROWS = 12, 24576  # TTS_GLOW_FORWARD_BLOCK_ROWS, _GRID_ROWS
 
 
 class TtsGanConvDesc(C.Structure):

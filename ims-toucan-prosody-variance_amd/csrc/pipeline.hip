@@ -10,6 +10,7 @@
 //   tts_decoder               decoder Conformer + feat_out (InferenceToucanTTS.py:238-239)
 //   tts_postnet               PostNet.forward + residual (PostNet.py:62-74, InferenceToucanTTS.py:241)
 //   tts_postflow              Glow.forward(infer=True) (Glow.py:342-391)
+//   tts_postflow_nll          Glow.forward(infer=False): the scorer's glow loss (include/toucan_score.h)
 //   tts_vocoder_bigvgan/_hifigan  InferenceBigVGAN.py:72-95 / InferenceAvocodo.py:69-80
 //   tts_synthesize_batch      all of the above for one ragged batch
 // Host work here is layout arithmetic (tile tables, offsets) and launch ordering; every FLOP is in the kernels.
@@ -74,6 +75,11 @@ struct Acoustic {
   ConvW feat_out, g_proj;
   struct { ConvW conv; const float *g, *b; } postnet[5];
   struct { ConvW start, end, cond; const float *winv, *an_bias, *an_logs; } flow[18];
+  // the forward direction (tts_postflow_nll), present in a scoring pipeline only: the InvConvNear weight itself, the `end` conv packed
+  // as a plain conv that writes [m | logs], and the constant part of a row's log-determinant
+  bool scoring = false;
+  struct { const float* wfwd; ConvW end_ml; } flow_fwd[18];
+  double flow_logdet = 0.0;
   struct { ConvW inl[4], res_skip[4]; } flowgrp[5];  // in / res-skip layers are shared inside groups of 4 blocks (Glow.py:325-327)
 };
 
@@ -170,6 +176,7 @@ struct Handle {
   Acoustic acoustic;  // resolved at the top of tts_encoder, vocoder at the top of tts_vocoder_*; tts_load_weights unresolves both
   Vocoder vocoder;
   Arena phone, frame, voc[2];
+  Arena nll;                      // tts_postflow_nll's own scratch (outside tts_workspace_bytes: synthesis handles never claim it)
   TableStore tabs[2][2];          // [0: acoustic stages, 1: vocoder][generation]
   int tab_gen[2] = {0, 0};
   int tab_which = 0;              // group of the stage entry that runs (set with split_mode)
@@ -585,6 +592,19 @@ int resolve_acoustic(Handle* h) {
       TTS_TRY(conv_of(h, p + "inl." + std::to_string(i), &m.flowgrp[g].inl[i]));
       TTS_TRY(conv_of(h, p + "res_skip." + std::to_string(i), &m.flowgrp[g].res_skip[i]));
     }
+  const Dev* logdet = find(h, "flow.logdet");
+  m.scoring = logdet != nullptr;
+  if (m.scoring) {
+    TTS_CHECK_ARG(logdet->dtype == 3 && logdet->bytes == sizeof(double), "weight 'flow.logdet' is not one float64 as two int32 words of host metadata");
+    memcpy(&m.flow_logdet, logdet->p, sizeof(double));
+    for (int b = 0; b < 18; ++b) {
+      const std::string p = "flow." + std::to_string(b) + ".";
+      TTS_TRY(fvec(h, p + "wfwd", &m.flow_fwd[b].wfwd));
+      TTS_TRY(conv_of(h, p + "end_ml", &m.flow_fwd[b].end_ml));
+      const ConvW& e = m.flow_fwd[b].end_ml;
+      TTS_CHECK_ARG(e.mode == TTS_MODE_LINEAR && e.cin == ATT && e.cout == 160 && e.taps == 1, "weight '%send_ml' is not a plain 1-tap 192 -> 160 conv", p.c_str());
+    }
+  }
   m.resolved = true;
   return TTS_OK;
 }
@@ -817,7 +837,7 @@ int pipeline_destroy(Handle* h) {
       }
       if (s.last_use) (void)hipEventDestroy(s.last_use);
     }
-  for (Arena* a : {&h->phone, &h->frame, &h->voc[0], &h->voc[1]})
+  for (Arena* a : {&h->phone, &h->frame, &h->voc[0], &h->voc[1], &h->nll})
     if (a->base) (void)hipFree(a->base);
   for (int s = 0; s < 2; ++s)
     if (h->ptab[s]) (void)hipFree(h->ptab[s]);
@@ -874,7 +894,7 @@ long long pipeline_workspace_bytes(const Handle* h, int B, int Lmax, int Tmax) {
 
 long long pipeline_workspace_claimed(const Handle* h) {
   if (!h) return 0;
-  return (long long)(h->phone.cap + h->frame.cap + h->voc[0].cap + h->voc[1].cap);
+  return (long long)(h->phone.cap + h->frame.cap + h->voc[0].cap + h->voc[1].cap + h->nll.cap);
 }
 
 // ---- stage A.1: encoder ----------------------------------------------------------------------------------------------
@@ -1192,6 +1212,92 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
   return TTS_OK;
 }
 
+// ---- the scorer's glow loss: PostFlow, forward pass (Glow.forward(infer=False), Glow.py:350-360) -----------------------------
+// gold [RF, 80] (row stride ld_gold) -> z by the 18 blocks in their own order: ActNorm, InvConvNear, coupling.  The conditioning and
+// the WaveNet of a coupling block are one function in both directions, so they are the conv launches of pipeline_postflow's fp32
+// branch; `end` runs as a plain conv into [m | logs], and tts_glow_forward_rows does the rest of a step: the coupling of block b
+// with ActNorm and InvConv of block b + 1 (19 launches).  tts_glow_nll_reduce turns z and the row log-determinants into the loss.
+// The frame arena is used from where tts_postnet left it and handed back as it was: tts_postflow can follow.  The mel is not touched.
+struct ArenaRewind {
+  Arena& a;
+  size_t off;
+  explicit ArenaRewind(Arena& a_) : a(a_), off(a_.off) {}
+  ~ArenaRewind() { a.off = off; }
+};
+
+int pipeline_postflow_nll(Handle* h, const float* gold, int ld_gold, float* loss, float* row_parts, float* z_out, hipStream_t st) {
+  TTS_CHECK_ARG(h, "tts_postflow_nll: null handle");
+  TTS_CHECK_ARG(!is16(h), "tts_postflow_nll: fp32 handles only (this one was created with precision %d)", h->cfg.precision);
+  TTS_CHECK_ARG(find(h, "flow.logdet") && find(h, "flow.0.wfwd") && find(h, "flow.0.end_ml.w"),
+                "tts_postflow_nll: the forward weights flow.<b>.wfwd, flow.<b>.end_ml and flow.logdet were not loaded (tts_load_weights; "
+                "NativePipeline(..., scoring=True) uploads them)");
+  TTS_CHECK_ARG(h->mel == h->cat && h->cat, "tts_postflow_nll: run tts_postnet first");
+  TTS_CHECK_ARG(gold && ld_gold >= 80 && loss, "tts_postflow_nll: null gold_mel / loss_out, or row stride %d < 80", ld_gold);
+  TTS_CHECK_RESOLVED(h, "tts_postflow_nll");
+  const Acoustic& m = h->acoustic;
+  TTS_CHECK_ARG(m.scoring, "tts_postflow_nll: the forward weights were not resolved: run tts_encoder again");
+  h->split_mode = 1;
+  h->tab_which = 0;
+  const Layout ls = h->lf.halved();
+  const int RF = h->lf.total, RS = RF / 2, B = h->lf.n();
+  long long live_rows = 0;
+  for (int n : ls.lengths) live_rows += n;
+  // its own scratch: [m | logs] of a block's `end` conv and one fp64 log-determinant per row
+  const size_t ml_bytes = ((size_t)RS * 160 * 4 + 255) & ~(size_t)255, ld_bytes = ((size_t)RS * 8 + 255) & ~(size_t)255;
+  TTS_TRY(arena_reserve(h->nll, ml_bytes + ld_bytes, st));
+  TTS_ALLOC(ml, h->nll, float, (size_t)RS * 160);
+  TTS_ALLOC(row_logdet, h->nll, double, RS);
+  TTS_TRY(hip_ok(hipMemsetAsync(h->nll.base, 0, ml_bytes + ld_bytes, st), "tts_postflow_nll: clear scratch"));  // (rows between utterances: m = logs = 0)
+  void* tab;
+  TTS_TRY(table_of(h, layout_key(h->lf, -2), st, [&] {  // (row_begin[B] | n_rows[B] | n_frames[B])
+    std::vector<int> host(3 * (size_t)B);
+    for (int u = 0; u < B; ++u) {
+      host[u] = ls.begins[u];
+      host[B + u] = ls.lengths[u];
+      host[2 * B + u] = h->lf.lengths[u];
+    }
+    return host;
+  }, &tab, nullptr));
+  const int* utt = static_cast<const int*>(tab);
+  Arena& a = h->frame;
+  ArenaRewind rewind(a);
+  TTS_ALLOC(x, a, float, (size_t)RS * 160);
+  TTS_TRY(hip_ok(hipMemcpy2DAsync(x, 80 * 4, gold, (size_t)ld_gold * 4, 80 * 4, RF, hipMemcpyDeviceToDevice, st), "tts_postflow_nll: gold mel"));
+  if (live_rows > 0) {  // (a batch of one-frame utterances launches nothing but the reduction)
+    TTS_ALLOC(g, a, float, (size_t)RF * ATT);
+    TTS_TRY(conv(h, m.g_proj, T2(h->cat, 80 + ATT), T2(g, ATT), h->lf, st));
+    TTS_ALLOC(hs, a, float, (size_t)RS * 2 * ATT);  // [hidden state | skip sum]
+    TTS_ALLOC(acts, a, float, (size_t)RS * ATT);
+    TTS_ALLOC(cond, a, float, (size_t)RS * 8 * ATT);
+    float* skip = hs + ATT;
+    TTS_TRY(tts_glow_forward_rows(x, 160, RS, nullptr, 0, nullptr, m.flow_fwd[0].wfwd, m.flow[0].an_bias, m.flow[0].an_logs, st));
+    for (int b = 0; b < 18; ++b) {
+      const auto& f = m.flow[b];
+      TTS_TRY(conv(h, f.start, T2(x, 160), T2(hs, 2 * ATT), ls, st));      // h = start(x0); the zero half clears the skip sum
+      TTS_TRY(conv(h, f.cond, T2(g, 2 * ATT), T2(cond, 8 * ATT), ls, st));  // squeeze of g = re-view [RS, 384]
+      for (int i = 0; i < 4; ++i) {
+        const ConvW &inl = m.flowgrp[b / 4].inl[i], &rs = m.flowgrp[b / 4].res_skip[i];
+        ConvOpt oi;
+        oi.preadd = cond + (size_t)i * 2 * ATT;
+        oi.ld_preadd = 8 * ATT;
+        TTS_TRY(conv(h, inl, T2(hs, 2 * ATT), T2(acts, ATT), ls, st, oi));
+        ConvOpt orr;
+        orr.accumulate = true;
+        TTS_TRY(conv(h, rs, T2(acts, ATT), i < 3 ? T2(hs, 2 * ATT) : T2(skip, 2 * ATT), ls, st, orr));
+      }
+      ConvOpt oe;
+      oe.fp32_only = true;
+      TTS_TRY(conv(h, m.flow_fwd[b].end_ml, T2(skip, 2 * ATT), T2(ml, 160), ls, st, oe));
+      const bool last = b == 17;
+      TTS_TRY(tts_glow_forward_rows(x, 160, RS, ml, 160, row_logdet, last ? nullptr : m.flow_fwd[b + 1].wfwd, last ? nullptr : m.flow[b + 1].an_bias,
+                                    last ? nullptr : m.flow[b + 1].an_logs, st));
+    }
+  }
+  TTS_TRY(tts_glow_nll_reduce(x, 160, row_logdet, utt, utt + B, utt + 2 * B, B, m.flow_logdet, loss, row_parts, st));
+  if (z_out) TTS_TRY(hip_ok(hipMemcpyAsync(z_out, x, (size_t)RS * 160 * 4, hipMemcpyDeviceToDevice, st), "tts_postflow_nll: z_out"));
+  return TTS_OK;
+}
+
 // where the batch's mel lives: packed [rows, 80] with row stride *ld; utterance u at frame_begin[u] (2-aligned), frames[u]
 // frames (one fewer than predicted for an odd count once the flow has run)
 int pipeline_mel(Handle* h, const float** mel, int* ld, int* frame_begins, int* frame_counts) {
@@ -1394,6 +1500,9 @@ int tts_decoder(TtsHandle* h, tts_stream_t stream) { return tts::stage_done(H(h)
 int tts_postnet(TtsHandle* h, tts_stream_t stream) { return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_postnet(H(h), ST(stream))); }
 int tts_postflow(TtsHandle* h, const float* z_noise, tts_stream_t stream) {
   return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_postflow(H(h), z_noise, ST(stream)));
+}
+int tts_postflow_nll(TtsHandle* h, const float* gold_mel, int32_t ld, float* loss_out, float* row_parts_out, float* z_out, tts_stream_t stream) {
+  return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_postflow_nll(H(h), gold_mel, ld, loss_out, row_parts_out, z_out, ST(stream)));
 }
 int tts_mel(TtsHandle* h, const float** mel, int32_t* ld, int32_t* frame_begins, int32_t* frame_counts) {
   return tts::pipeline_mel(H(h), mel, ld, frame_begins, frame_counts);

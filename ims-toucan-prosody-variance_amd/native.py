@@ -26,10 +26,13 @@ def ptr(t):
 class NativePipeline:
     """One handle per (process, device): acoustic model + (optionally) one vocoder."""
 
-    def __init__(self, acoustic_sd, vocoder_sd=None, vocoder_kind=None, device="cuda", precision="f32", pmax=1024, vocoder_precision=None):
+    def __init__(self, acoustic_sd, vocoder_sd=None, vocoder_kind=None, device="cuda", precision="f32", pmax=1024, vocoder_precision=None,
+                 scoring=False):
         """precision: of the acoustic model ("f32" | "bf16" | "f16").  vocoder_precision (default: the same): a different one gives
         the vocoder its own handle - e.g. precision="f32", vocoder_precision="f16": the mel keeps the exact-parity arithmetic
-        (mel L1 <= 1e-5 against the reference) and the vocoder, the bulk of the work, runs on the 16-bit matrix cores."""
+        (mel L1 <= 1e-5 against the reference) and the vocoder, the bulk of the work, runs on the 16-bit matrix cores.
+        scoring: also upload what the PostFlow needs in the forward direction (tts_postflow_nll: ``flow.<b>.wfwd``, ``flow.<b>.end_ml``,
+        ``flow.logdet``); fp32 only.  Without it a handle holds exactly the synthesis weights."""
         self.lib = capi.lib()
         if not isinstance(self.lib, C.CDLL):
             raise capi.ToucanHipError("the stage API needs the real libtoucan_hip.so (the test emulator only restates kernels)")
@@ -59,6 +62,11 @@ class NativePipeline:
             capi.check(self.lib.tts_create(C.byref(cfg), C.byref(self.h)), "tts_create")
             self._target = self.h  # the handle _load() uploads to
             self._upload_acoustic(ac)
+            self.scoring = bool(scoring)
+            if self.scoring:
+                if self.precision != "f32":
+                    raise capi.ToucanHipError(f"scoring=True needs precision 'f32' (tts_postflow_nll), not {self.precision!r}")
+                self._upload_flow_forward(packing.fold_weight_norm(acoustic_sd))
             if split:
                 self.h_voc = C.c_void_p()
                 cfg_v = capi.TtsConfig(int(self.multilingual), int(self.multispeaker), kind_code, compute_v, stb, post_b)
@@ -156,6 +164,17 @@ class NativePipeline:
                 for i in range(4):
                     self._conv(f"flowgrp.{b // 4}.inl.{i}", blk["inl"][i])
                     self._conv(f"flowgrp.{b // 4}.res_skip.{i}", blk["res_skip"][i])
+
+    def _upload_flow_forward(self, sd):
+        """The PostFlow's forward direction (include/toucan_score.h tts_postflow_nll): per block the InvConvNear weight itself and the
+        coupling's ``end`` conv packed as a plain conv (the synthesis pack fuses the reverse affine step into it); the float64 constant
+        of a row's log-determinant as host metadata (two int32 words)."""
+        for b in range(18):
+            self._load(f"flow.{b}.wfwd", torch.from_numpy(packing.invconv_forward(sd, f"post_flow.flows.{3 * b + 1}.")))
+            pcp = f"post_flow.flows.{3 * b + 2}."
+            self._conv(f"flow.{b}.end_ml", packing.pack_conv(sd[pcp + "end.weight"], sd[pcp + "end.bias"], "cpu"))
+        const = np.array([packing.glow_logdet_constant(sd)], dtype=np.float64)
+        self._load("flow.logdet", torch.from_numpy(const.view(np.int32).copy()))
 
     def _upload_vocoder(self, voc):
         self._conv("voc.pre", voc.pre)

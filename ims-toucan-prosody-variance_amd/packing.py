@@ -182,6 +182,25 @@ def invconv_inverse(sd, prefix):
     return np.linalg.inv(w.astype(np.float32).astype(np.float64)).astype(np.float32)
 
 
+def invconv_forward(sd, prefix):
+    """Glow.py:130-135: the weight of the forward pass itself, W = P (L*mask + I) (U*mask^T + diag(sign*exp(log_s))), formed in
+    float64 like its inverse above (which is the inverse of this fp32 matrix)."""
+    f = lambda k: _np(sd[prefix + k]).astype(np.float64)
+    l = f("l") * f("l_mask") + f("eye")
+    u = f("u") * f("l_mask").T + np.diag(f("sign_s") * np.exp(f("log_s")))
+    return (f("p") @ (l @ u)).astype(np.float32)
+
+
+def glow_logdet_constant(sd, n_blocks=18, prefix="post_flow.flows."):
+    """The part of a squeezed row's log-determinant that no input changes, in float64: over the blocks, sum of the ActNorm's logs
+    (Glow.py:35) + 40 * sum of the InvConvNear's log_s (:107-108: c / n_split = 160 / 4 groups per row)."""
+    total = 0.0
+    for b in range(n_blocks):
+        total += float(_np(sd[f"{prefix}{3 * b}.logs"]).astype(np.float64).sum())
+        total += 40.0 * float(_np(sd[f"{prefix}{3 * b + 1}.log_s"]).astype(np.float64).sum())
+    return total
+
+
 def rel_pos_encoding(pmax, d=192):
     """Rows p = -(pmax-1) .. pmax-1 of the sinusoid table (Layers/PositionalEncoding.py:90-117), fp32 like the reference."""
     pos = np.arange(-(pmax - 1), pmax, dtype=np.float32)[:, None]

@@ -5,7 +5,9 @@ problematic samples.
   transcript).  Logits: ``align.AlignerEngine.logits``; the loss: ``tts_ctc_loss`` (csrc/score.hip).
 * ``TTSScorer`` (:79-199): the acoustic model's teacher-forced loss per utterance of ``fast_train_cache.pt`` (a high loss flags bad
   audio), and the removal of the worst samples from the cache.  Style embedding: ``style.StyleEngine``; forward pass: the stage API
-  (``tts_encoder``, ``tts_teacher_forced``, ``tts_decoder``, ``tts_postnet``); the four losses: ``tts_score_losses``.
+  (``tts_encoder``, ``tts_teacher_forced``, ``tts_decoder``, ``tts_postnet``); the four losses: ``tts_score_losses``.  On request
+  (``score(..., include_glow=True)``) the fifth loss of ``ToucanTTS.forward``, which the reference's scorer leaves out
+  (``run_glow=False``): the negative log-likelihood of the gold spectrogram under the PostFlow, ``tts_postflow_nll``.
 
 Both score ragged batches of utterances sorted by length (``score(..., batch_size=32)``, an additive argument); results are per file
 path, in the cache's order.  An utterance's score does not depend on its batch: bit for bit for the CTC loss, to rounding order for
@@ -215,12 +217,14 @@ class TTSScorer:
         self.device = device
         self.path_to_score = dict()
         self.path_to_id = dict()
+        self.path_to_parts = dict()
+        self.path_to_row_scores = dict()
         self.nans = list()
         self.nan_indexes = list()
         # the reference's fallbacks ToucanTTS(lang_embs=None) / (lang_embs=None, utt_embed_dim=None) (:95-104): the pipeline reads the
         # variant off the state dict
         weights = _to_numpy_sd(_load_checkpoint(path_to_model)["model"])
-        self.pipe = native.NativePipeline(weights, None, None, device, precision="f32")
+        self.pipe = native.NativePipeline(weights, None, None, device, precision="f32", scoring=True)
         self.style_embedding_function = style.StyleEngine(_to_numpy_sd(_load_checkpoint(path_to_embedding_checkpoint)["style_emb_func"]),
                                                           self.pipe.device)
         self.nans_removed = False
@@ -229,9 +233,13 @@ class TTSScorer:
         self.last_phase_ms = {}
 
     @torch.inference_mode()
-    def forward_batch(self, items, lang_id):
+    def forward_batch(self, items, lang_id, include_glow=False, keep_row_scores=False):
         """One ragged batch through the teacher-forced forward pass and the loss kernel.  items: dicts of read_tts_cache.  -> dict with
-        ``losses`` [B, 4] (l1, duration, pitch, energy; device) and the device buffers of the pass (predictions, packed mels, layouts)."""
+        ``losses`` [B, 4] (l1, duration, pitch, energy; device) and the device buffers of the pass (predictions, packed mels, layouts).
+        include_glow: ``losses`` is [B, 5], the glow loss last (tts_postflow_nll: the PostFlow run forward on the gold mel, conditioned
+        on the pass's own PostNet output; NaN for an utterance of fewer than two frames).  keep_row_scores (with include_glow):
+        ``glow_rows`` is the float32 device tensor [total frames / 2, 2] of tts_glow_nll_reduce's row parts, utterance u at row
+        ``rag_frame.begins[u] // 2`` with ``T // 2`` rows (``row_scores_of``)."""
         pipe = self.pipe
         dev, lib = pipe.device, pipe.lib
         with torch.cuda.device(dev):
@@ -280,43 +288,94 @@ class TTSScorer:
             capi.check(lib.tts_score_losses(ptr(before), 80, after, int(ld.value), ptr(gold), 80, ptr(fb), ptr(nf), ptr(pred[0]), ptr(pred[1]),
                                             ptr(pred[2]), ptr(packed["gd"]), ptr(packed["gp"]), ptr(packed["ge"]), ptr(pb), ptr(npd), B,
                                             ptr(losses), st), "tts_score_losses")
+            glow_rows = None
+            if include_glow:
+                mark("glow")
+                glow = torch.empty(B, dtype=torch.float32, device=dev)
+                if keep_row_scores:
+                    glow_rows = torch.zeros(RF // 2, 2, dtype=torch.float32, device=dev)
+                capi.check(lib.tts_postflow_nll(pipe.h, ptr(gold), 80, ptr(glow), ptr(glow_rows), None, st), "tts_postflow_nll")
+                losses = torch.cat([losses, glow[:, None]], dim=1)
             mark("end")
             if ev:
                 torch.cuda.synchronize(dev)
                 for (name, e0), (_, e1) in zip(ev[:-1], ev[1:]):
                     self.last_phase_ms[name] = self.last_phase_ms.get(name, 0.0) + e0.elapsed_time(e1)
-            return dict(losses=losses, pred=pred, before=before, gold=gold, rag_frame=rag_f, rag_phone=rag_p, packed=packed)
+            return dict(losses=losses, pred=pred, before=before, gold=gold, rag_frame=rag_f, rag_phone=rag_p, packed=packed, glow_rows=glow_rows)
 
-    def score_items(self, items, lang_id, batch_size=32):
-        """items: dicts of read_tts_cache -> numpy float32 [n, 4] losses (l1, duration, pitch, energy) in the items' order."""
-        out = np.zeros((len(items), 4), dtype=np.float32)
+    @staticmethod
+    def row_scores_of(out, index):
+        """The row parts [T // 2, 2] (numpy float32) of utterance ``index`` of a forward_batch(..., keep_row_scores=True) result."""
+        rag = out["rag_frame"]
+        r0, n = int(rag.begins[index]) // 2, int(rag.lengths[index]) // 2
+        return out["glow_rows"][r0:r0 + n].cpu().numpy()
+
+    def score_items(self, items, lang_id, batch_size=32, include_glow=False, keep_row_scores=False):
+        """items: dicts of read_tts_cache -> numpy float32 [n, 4] losses (l1, duration, pitch, energy) in the items' order; with
+        include_glow [n, 5], the glow loss last.  keep_row_scores (with include_glow): ``self.last_row_scores`` is the list of the
+        items' row parts, each float32 [T // 2, 2] (see ``score``)."""
+        out = np.zeros((len(items), 5 if include_glow else 4), dtype=np.float32)
         self.last_phase_ms = {}
+        self.last_row_scores = [None] * len(items) if include_glow and keep_row_scores else None
         for batch in _batches([it["spec"].shape[0] for it in items], batch_size):
-            out[batch] = self.forward_batch([items[i] for i in batch], lang_id)["losses"].cpu().numpy()
+            if not include_glow:
+                out[batch] = self.forward_batch([items[i] for i in batch], lang_id)["losses"].cpu().numpy()
+                continue
+            res = self.forward_batch([items[i] for i in batch], lang_id, include_glow=True, keep_row_scores=keep_row_scores)
+            out[batch] = res["losses"].cpu().numpy()
+            if self.last_row_scores is not None:
+                for k, i in enumerate(batch):
+                    self.last_row_scores[i] = self.row_scores_of(res, k)
         return out
 
-    def score(self, path_to_toucantts_dataset, lang_id, batch_size=32):
+    def score(self, path_to_toucantts_dataset, lang_id, batch_size=32, include_glow=False, keep_row_scores=False):
         """
         call this to update the path_to_score dict with scores for this dataset
+
+        include_glow: the score is l1 + duration + pitch + energy + glow, the five losses of the reference's ``ToucanTTS.forward``
+        with ``run_glow=True`` (its own scorer passes ``run_glow=False``), and ``path_to_parts[filepath]`` holds the five values.  The
+        glow loss is the negative log-likelihood per spectrogram bin of the gold spectrogram under the PostFlow; it reacts to clicks,
+        clipping and noise bursts that the l1 average smooths over.
+
+        keep_row_scores (with include_glow): ``path_to_row_scores[filepath]`` is a float32 array [T // 2, 2]; row r covers the frames
+        2r and 2r + 1 (an odd last frame belongs to no row: the flow's squeeze drops it).  Column 0 is the row's prior term,
+        sum over its 160 latent values of z^2 / 2 + log(2 pi) / 2; column 1 is the row's log-determinant.  They add up to the loss as
+        ``glow = rows[:, 0].sum() / (160 * (T // 2)) - rows[:, 1].sum() / (80 * T)``: a row whose column 0 is large, or whose column 1
+        is small, is where the file is unlikely.
         """
         lid = get_language_id(lang_id)
         if lid is None:
             raise ValueError(f"language {lang_id!r} has no id (Preprocessing/TextFrontend.py:490-524)")
+        if keep_row_scores and not include_glow:
+            raise ValueError("keep_row_scores=True needs include_glow=True: the row scores are the parts of the glow loss")
         datapoints, items = read_tts_cache(path_to_toucantts_dataset)
-        self.record_scores(ScoredCorpus(path_to_toucantts_dataset, datapoints, lid), items, self.score_items(items, lid, batch_size))
+        parts = self.score_items(items, lid, batch_size, include_glow=include_glow, keep_row_scores=keep_row_scores)
+        self.record_scores(ScoredCorpus(path_to_toucantts_dataset, datapoints, lid), items, parts, include_glow=include_glow)
+        self.path_to_row_scores = dict()
+        if keep_row_scores:
+            self.path_to_row_scores = {it["filepath"]: rows for it, rows in zip(items, self.last_row_scores)}
 
-    def record_scores(self, corpus, items, parts):
+    def record_scores(self, corpus, items, parts, include_glow=False):
         """The bookkeeping of score(): parts [n, 4] (l1, duration, pitch, energy) of the items of ``corpus`` -> path_to_score,
-        path_to_id, nans, nan_indexes, current_dset."""
+        path_to_id, path_to_parts, nans, nan_indexes, current_dset.  include_glow: parts [n, 5], the glow loss last, and the score is
+        the sum of all five."""
+        parts = np.asarray(parts)
+        if parts.ndim != 2 or parts.shape[1] != (5 if include_glow else 4):
+            raise ValueError(f"parts {parts.shape}: expected [n, {5 if include_glow else 4}] with include_glow={bool(include_glow)}")
         self.current_dset = corpus
         self.nans = list()
         self.nan_indexes = list()
         self.path_to_score = dict()
         self.path_to_id = dict()
+        self.path_to_parts = dict()
         for index, it in enumerate(items):
-            l1, dur, pitch, energy = (np.float32(v) for v in parts[index])
-            loss = l1 + dur + pitch + energy  # we omit the glow loss (fp32, the reference's order)
+            l1, dur, pitch, energy = (np.float32(v) for v in parts[index][:4])
+            # fp32, the reference's order (Scorer.py:131); its scorer stops here (run_glow=False), include_glow adds the fifth loss
+            loss = l1 + dur + pitch + energy
+            if include_glow:
+                loss = loss + np.float32(parts[index][4])
             filepath = it["filepath"]
+            self.path_to_parts[filepath] = tuple(float(np.float32(v)) for v in parts[index])
             if np.isnan(loss):
                 self.nans.append(filepath)
                 self.nan_indexes.append(index)

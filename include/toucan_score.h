@@ -58,6 +58,49 @@ int tts_teacher_forced(TtsHandle* h, const float* gold_pitch, const float* gold_
  * (row stride ld_dst >= 80).  Valid after tts_decoder. */
 int tts_copy_decoder_mel(TtsHandle* h, float* dst, int32_t ld_dst, tts_stream_t stream);
 
+/* ---- the glow loss: the PostFlow in the forward direction (csrc/glow_forward.hip; Glow.py:342-391 with infer=False) ---- */
+
+/* The per-row part of one step of the forward pass, in place on the squeezed rows x [rows, 160] (row stride ldx >= 160; a row is
+ * [frame 2r | frame 2r+1]).  Two halves, each optional (not both absent):
+ *   ml (with ld_ml, row_logdet): the coupling of block b on the output [m | logs] of its `end` conv (CouplingBlock.forward :266-267):
+ *     x[:, 80:] = m + exp(logs) * x[:, 80:], and row_logdet[r] += sum_80 logs[r] (fp64, the same order for every row);
+ *   w (with an_bias, an_logs): ActNorm then InvConvNear of block b + 1 (:34, :102-127): x = bias + exp(an_logs) * x, then the four
+ *     channels 2g, 2g+1, 80+2g, 80+2g+1 of every group g are mixed by the FORWARD weight w [4][4] (packing.invconv_forward), the
+ *     same channels tts_glow_invconv_actnorm mixes with the inverse.
+ * A row is computed in fp64 from its fp32 inputs and rounded once on the way out (with both halves: once, after the mix), and
+ * depends on nothing but that row: any batch layout gives the same bits.  16-byte loads and stores where x and ml are 16-byte
+ * aligned with strides divisible by four, scalar ones otherwise.  One workgroup takes TTS_GLOW_FORWARD_BLOCK_ROWS rows; past
+ * TTS_GLOW_FORWARD_GRID_ROWS rows the grid strides. */
+#define TTS_GLOW_FORWARD_BLOCK_ROWS 12
+#define TTS_GLOW_FORWARD_GRID_ROWS 24576
+int tts_glow_forward_rows(float* x, int32_t ldx, int32_t rows, const float* ml, int32_t ld_ml, double* row_logdet, const float* w,
+                          const float* an_bias, const float* an_logs, tts_stream_t stream);
+
+/* The glow loss per utterance from the latent z [rows, 160] (row stride ldz) and the rows' data-dependent log-determinants, one
+ * workgroup per utterance, fp64 in an order fixed by the utterance alone.  Utterance u: rows row_begin[u] ... (n_rows[u] of them),
+ * n_frames[u] unsqueezed frames.  Per row r: prior[r] = sum_160 (z^2 / 2 + log(2 pi) / 2) and logdet[r] = row_logdet[r] +
+ * logdet_per_row (the constant part: sum over the blocks of sum an_logs + 40 sum log_s, formed by the host in float64);
+ *   loss[u] = sum_r prior[r] / (160 n_rows) - sum_r logdet[r] / (80 n_frames)            (Glow.py:354-356)
+ * - the two divisors differ for an odd frame count, as in the reference (the mean runs over the truncated z, the log-determinant
+ * is divided by the unsqueezed length).  n_rows == 0 gives NaN (the mean of an empty tensor).  row_parts (or NULL): float32
+ * [rows, 2] = (prior[r], logdet[r]) for the rows of the utterances; other rows are left alone. */
+int tts_glow_nll_reduce(const float* z, int32_t ldz, const double* row_logdet, const int32_t* row_begin, const int32_t* n_rows,
+                        const int32_t* n_frames, int32_t batch, double logdet_per_row, float* loss, float* row_parts, tts_stream_t stream);
+
+/* ---- stage API: the glow loss (csrc/pipeline.hip) ---- */
+
+/* After tts_postnet, on an fp32 handle that holds the forward weights (flow.<b>.wfwd [4][4], flow.<b>.end_ml: the `end` conv packed
+ * as a plain 192 -> 160 conv, flow.logdet: the float64 constant as two int32 words of host metadata - native.NativePipeline uploads
+ * them with scoring=True): the negative log-likelihood of gold_mel under the PostFlow conditioned on the teacher-forced decoder
+ * output, ToucanTTS.py:349-353 with run_glow=True.  gold_mel: [total frames, 80] in the frame layout of the batch (row stride ld >=
+ * 80; utterance u at frame_begin[u]; what the rows between utterances hold changes no result).  g_proj, start, cond, in_layer and
+ * res_skip are the conv launches of tts_postflow's fp32 branch; 19 tts_glow_forward_rows launches and one tts_glow_nll_reduce.
+ * loss_out: float32 [B].  row_parts_out (or NULL): float32 [total frames / 2, 2] as tts_glow_nll_reduce writes it.  z_out (or NULL):
+ * the latent [total frames / 2, 160] = [total frames, 80] - tts_postflow on the same handle state with z_out as z_noise returns
+ * gold_mel on the frames 0 .. 2 (T / 2) - 1 of each utterance.  An utterance of fewer than two frames gets NaN.  The handle's mel
+ * (tts_mel, tts_copy_mel) stays the PostNet's; the scratch this entry adds is its own arena, outside tts_workspace_bytes. */
+int tts_postflow_nll(TtsHandle* h, const float* gold_mel, int32_t ld, float* loss_out, float* row_parts_out, float* z_out, tts_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

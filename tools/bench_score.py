@@ -4,6 +4,10 @@ memory.  Prints one JSON line: utterances/s of each scorer (median of --steps pa
 aligner logits / CTC, and style embedding / acoustic stages / loss kernel, from HIP events.
 
     python tools/bench_score.py --utterances 256 --batch 32 --steps 3 --warmup 1
+
+``--glow`` adds a phase after those: passes of the TTS scorer over the same corpus with and without ``include_glow``, alternated, and
+the keys ``glow_*`` in the JSON line (the pass with the glow loss, the pass without it measured beside it, the HIP-event time of
+``tts_postflow_nll``, and its cost per utterance).  Without the flag the output is what it was.
 """
 import argparse
 import json
@@ -26,6 +30,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--glow", action="store_true", help="also time the TTS scorer with include_glow=True against without, alternated")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     with tempfile.TemporaryDirectory() as d:
@@ -66,6 +71,20 @@ def main():
         "tts_ms_style": r(pt.get("style", 0.0)), "tts_ms_acoustic": r(pt.get("acoustic", 0.0)), "tts_ms_loss": r(pt.get("loss", 0.0)),
         "gpu": torch.cuda.get_device_name(dev),
     }
+    if args.glow:
+        wall, glow_ms = {False: [], True: []}, []
+        for step in range(args.warmup + args.steps):
+            for on in (False, True):  # alternated: both see the same clocks and cache state
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                tts.score_items(tts_items, lid, args.batch, include_glow=on)
+                if step >= args.warmup:
+                    wall[on].append((time.perf_counter() - t0) * 1e3)
+                    if on:
+                        glow_ms.append(tts.last_phase_ms.get("glow", 0.0))
+        w0, w1, g = float(np.median(wall[False])), float(np.median(wall[True])), float(np.median(glow_ms))
+        out.update({"glow_tts_utterances_per_s": round(1e3 * n / w1, 1), "glow_tts_ms_per_pass": r(w1), "glow_off_ms_per_pass": r(w0),
+                    "glow_ms_postflow_nll": r(g), "glow_ms_per_utterance": r(g / n)})
     print(json.dumps(out))
 
 
