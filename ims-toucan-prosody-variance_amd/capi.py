@@ -95,6 +95,7 @@ class TtsConfig(C.Structure):
 IO_X_BF16, IO_Y_BF16, IO_RES_BF16, IO_F16 = 1, 2, 4, 8
 IO_SPLIT_K = 16  # tts_conv1d, fp32: the caller accepts the split-K form on small grids (the frame stages of the fp32 acoustic model do)
 IO_SPLIT_K_ALWAYS = 32  # ... at every grid size (its phoneme stages: one arithmetic upstream of the rounded durations whatever the batch)
+IO_POLYPHASE = 64  # tts_conv1d, wide tile (tile_rows 256): a 3-tap polyphase up-sampler whose structural zeros the kernel leaves out
 ATT_KEY_SPLIT, ATT_KEY_SPLIT_ALWAYS = 1, 2  # tts_relpos_attention flags (include/toucan_tts.h)
 
 # symbol -> (restype, argtypes); mirrors include/toucan_tts.h one to one

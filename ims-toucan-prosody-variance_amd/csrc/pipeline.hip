@@ -28,6 +28,8 @@
 
 namespace tts {
 
+const char* conv1d_wide_reject(const TtsConvDesc& d);  // conv1d_wide.hip: nullptr when the call may take the wide form
+
 namespace {
 
 constexpr int ATT = 192, HEADS = 4, DK = 48;
@@ -444,6 +446,19 @@ struct ConvOpt {
   const float *snake_alpha = nullptr, *snake_beta = nullptr, *snake_filt = nullptr;
 };
 
+// CUs of the current device (asked once per device)
+int device_cus() {
+  static int cus[64] = {0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  int& c = cus[dev & 63];
+  if (c == 0 && (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1)) {
+    (void)hipGetLastError();
+    c = 256;
+  }
+  return c;
+}
+
 int conv(Handle* h, const ConvW& cw, T2 x, T2 y, const Layout& l, hipStream_t st, const ConvOpt& o = ConvOpt()) {
   int tile_rows = cw.tile_rows;
   if (h->small_tile_blocks && cw.small_tile_rows && !cw.small_only) {
@@ -484,10 +499,25 @@ int conv(Handle* h, const ConvW& cw, T2 x, T2 y, const Layout& l, hipStream_t st
   // utterance's result there does not depend on the batch it is in, bit for bit - tests/test_gpu_e2e.py asserts it)
   if (h->split_mode && !o.no_split_k && !is16(h) && d.compute == TTS_COMPUTE_F32)
     d.io_flags |= h->split_mode == 2 ? TTS_IO_SPLIT_K_ALWAYS : TTS_IO_SPLIT_K;
+  if (cw.algo_taps == 2 && cw.taps == 3) d.io_flags |= TTS_IO_POLYPHASE;  // a transposed conv packed as a polyphase conv (packing.pack_conv_transpose)
+  // The wide form (256 x 256 tiles, conv1d_wide.hip) where the call is eligible, its grid gives every CU a workgroup and the shape
+  // measured faster on it (one workgroup per CU exposes the epilogue, so the contraction has to be long - at
+  // least 28 (slab, tap) steps - or the polyphase skip has to drop whole steps, which takes two or more column tiles); the results
+  // are bit-identical to the other forms, so this is a speed choice only (same rule as engine.Ops.conv).
+  const bool wide_pays = (cw.cin / 64) * cw.taps >= 28 || ((d.io_flags & TTS_IO_POLYPHASE) && cw.wn >= 512);
+  if (cw.tile_rows != 256 && wide_pays && conv1d_wide_reject(d) == nullptr) {
+    long long t256 = 0;
+    for (int n : l.lengths) t256 += (n + 255) / 256;
+    if (t256 * (cw.wn / 256) >= device_cus()) {
+      tile_rows = 256;
+      TTS_TRY(tiles_of(h, l, tile_rows, st, &tt));
+    }
+  }
   d.tiles = tt.dev; d.n_tiles = tt.n; d.tile_rows = tile_rows;
   if (h->prof_on) {  // same class names and algorithmic work as profiling.py (kernel_class / ConvTimer.add)
     const bool dual = cw.mode != TTS_MODE_LINEAR;
-    const int bm = tile_rows != cw.tile_rows ? tile_rows : cw.tile_rows, bn = tile_rows != cw.tile_rows ? 64 : cw.n_tile;
+    const bool wide = tile_rows == 256 && cw.tile_rows != 256;
+    const int bm = tile_rows != cw.tile_rows ? tile_rows : cw.tile_rows, bn = wide ? 256 : (tile_rows != cw.tile_rows ? 64 : cw.n_tile);
     char name[96];
     int nlen = snprintf(name, sizeof(name), "conv1d_%s<%dx%d%s>", d.compute == TTS_COMPUTE_F32 ? "f32" : (d.compute == TTS_COMPUTE_BF16 ? "bf16" : (d.compute == TTS_COMPUTE_F16 ? "f16" : "f32x3")),
                         bm, bn, dual ? ",dual" : "");

@@ -34,6 +34,18 @@ def _f16_flag(*ts):
     return capi.IO_F16 if any(t is not None and t.dtype == torch.float16 for t in ts) else 0
 
 
+def _wide_ok(d, cw, x, y, res):
+    """May this tts_conv1d call take the wide form (tile_rows 256)?  The rule of include/toucan_tts.h, which the library checks
+    again: a plain 16-bit conv on whole 64-channel slabs and 256-column tiles whose window fits the LDS."""
+    ts = [t for t in (x, y, res) if t is not None]
+    dt = torch.float16 if d.compute == COMPUTE_F16 else torch.bfloat16
+    return (d.compute in (COMPUTE_BF16, COMPUTE_F16) and cw.mode == MODE_LINEAR and all(t.dtype == dt for t in ts)
+            and d.pre_act == PRE_NONE and not (d.seqvec or d.preadd or d.aux)
+            and cw.cin == cw.cin_pad and cw.cin % 64 == 0 and cw.wn % 256 == 0 and cw.cout % 4 == 0
+            and all(_ld(t) % 8 == 0 and t.data_ptr() % 16 == 0 for t in ts)
+            and 2 * ((256 + (cw.taps - 1) * cw.dil + 7) // 8 * 8) * 128 + 66 * 1024 <= 160 * 1024)
+
+
 def precision_of(bf16, precision):
     """(`bf16` flag of the older API, `precision` in {None, "f32", "f32x3", "bf16", "f16"}) -> (name, pack argument, compute, torch
     dtype of the 16-bit tensors).  "f32x3": fp32 tensors everywhere, the dense products of the frame stages as three fp16 MFMAs on
@@ -78,6 +90,8 @@ class Ops:
         # convs / key-split attention at every grid size (phoneme stages: everything upstream of the rounded durations keeps one
         # arithmetic whatever the batch), 1 = on small grids only (frame stages), 0 = never (vocoder: chunked == whole)
         self.split_k = 0
+        # CUs of the device: eligible 16-bit convs whose 256 x 256 grid reaches it take the wide form (0: never - the host emulator)
+        self.n_cus = torch.cuda.get_device_properties(self.device).multi_processor_count if isinstance(self.lib, C.CDLL) else 0
         self.small_tile_blocks = 1536  # regular conv grids below this many workgroups switch to the 64 x 64 small-batch form (0: never)
         self._fir_tabs = {}
         self.default_compute = COMPUTE_F32  # convs whose weights carry a 16-bit copy run on bf16 / fp16 MFMA when this is not COMPUTE_F32
@@ -91,11 +105,15 @@ class Ops:
         return torch.empty(*shape, dtype=dtype, device=self.device)
 
     def conv(self, cw, x, y, rag, pre=PRE_NONE, pre_slope=0.0, act=ACT_NONE, alpha=1.0, seqvec=None, preadd=None, res=None,
-             res_scale=1.0, aux=None, accumulate=False, compute=None, snake=None, split_k=True):
+             res_scale=1.0, aux=None, accumulate=False, compute=None, snake=None, split_k=True, tile_rows=None):
+        """tile_rows: None = the form the grid heuristics pick; 64 / cw.tile_rows / 256 = that form whatever the grid (tests: the
+        forms are bit-identical; an ineligible call is an argument error)."""
         if compute is None:
             compute = self.default_compute
-        tile_rows = cw.tile_rows
-        if self.small_tile_blocks and cw.small_tile_rows and not cw.small_only:
+        forced = tile_rows is not None
+        if not forced:
+            tile_rows = cw.tile_rows
+        if not forced and self.small_tile_blocks and cw.small_tile_rows and not cw.small_only:
             # grid of the regular form; when it cannot fill the chip, the 64 x 64 form runs ~3x more workgroups
             cols = cw.wn if cw.mode == MODE_LINEAR else cw.half_pad
             if -(-rag.total_rows // cw.tile_rows) * (cols // cw.n_tile) < self.small_tile_blocks:
@@ -133,6 +151,16 @@ class Ops:
             # same rule as pipeline.hip conv(): the fp32 configuration only - the fp32 layers of a 16-bit configuration keep one
             # accumulation order at every batch size (an utterance's result there does not depend on the batch it is in, bit for bit)
             d.io_flags |= capi.IO_SPLIT_K_ALWAYS if self.split_k == 2 else capi.IO_SPLIT_K
+        if cw.algo_taps == 2 and cw.taps == 3:
+            d.io_flags |= capi.IO_POLYPHASE  # a transposed conv packed as a polyphase conv (packing.pack_conv_transpose)
+        # The wide form (256 x 256 tiles) where the call is eligible, its grid gives every CU a workgroup and the shape measured faster
+        # on it (a contraction of at least 28 (slab, tap) steps, or a polyphase skip that drops whole steps): bit-identical to the
+        # other forms, a speed choice only (same rule as pipeline.hip conv())
+        wide_pays = (cw.cin // 64) * cw.taps >= 28 or (bool(d.io_flags & capi.IO_POLYPHASE) and cw.wn >= 512)
+        if not forced and self.n_cus and cw.tile_rows != 256 and wide_pays and _wide_ok(d, cw, x, y, res):
+            if sum(-(-n // 256) for n in rag.lengths) * (cw.wn // 256) >= self.n_cus:
+                tile_rows = 256
+                tiles, n_tiles = rag.tiles(tile_rows)
         d.tiles, d.n_tiles, d.tile_rows = tiles.data_ptr(), n_tiles, tile_rows
         tm = self.timer
         if tm is not None and tm.wants(cw, d.compute, tile_rows):

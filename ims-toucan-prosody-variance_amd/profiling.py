@@ -12,11 +12,12 @@ from . import capi
 
 def kernel_class(cw, compute, tile_rows=None):
     """Name of the conv1d instantiation a launch runs: precision, tile (the 64 x 64 small-batch form when the host asked
-    for 64-row tiles on a shape whose regular form is larger) and dual-accumulator mode."""
+    for 64-row tiles on a shape whose regular form is larger, the 256 x 256 wide form when it asked for 256-row tiles) and
+    dual-accumulator mode."""
     dual = cw.mode != capi.MODE_LINEAR
     bm, bn = cw.tile_rows, cw.n_tile
     if tile_rows is not None and tile_rows != cw.tile_rows:
-        bm, bn = tile_rows, 64
+        bm, bn = tile_rows, (256 if tile_rows == 256 else 64)  # the wide form, or the small-batch form
     prec = {capi.COMPUTE_F32: "f32", capi.COMPUTE_BF16: "bf16", capi.COMPUTE_F16: "f16", capi.COMPUTE_F32X3: "f32x3"}[compute]
     return "conv1d_%s<%dx%d%s>" % (prec, bm, bn, ",dual" if dual else "")
 

@@ -58,6 +58,9 @@ typedef struct {
 #define TTS_IO_SPLIT_K_ALWAYS 32 /* tts_conv1d, fp32 only: the split-K form at EVERY grid size wherever the conv itself is eligible
                              (one arithmetic whatever the batch: the phoneme stages of the fp32 acoustic model, whose rounded durations
                              must not depend on the batch an utterance is in) */
+#define TTS_IO_POLYPHASE 64 /* tts_conv1d, wide tile only (tile_rows 256): the weights are a transposed conv packed as a 3-tap polyphase
+                             conv - taps == 3, tap 0 multiplies only zeros for the columns >= wn / 2 and tap 2 for the columns < wn / 2 -
+                             and the kernel leaves those products out (finite results unchanged; an exact zero may change sign) */
 /* tts_relpos_attention flags (fp32 kernel): the key-split form - four wavefronts share one block of 32 queries, split the keys
  * and merge (max, sum, output) in LDS: four interleaved partial sums, i.e. another rounding order than the plain form */
 #define TTS_ATT_KEY_SPLIT 1        /* on grids of at most 64 workgroups (batch 1): the result then depends on the grid at rounding level */
@@ -103,7 +106,7 @@ typedef struct {
                           w must be packed in the matching element type */
   int32_t io_flags;    /* TTS_IO_* bits: which of x / y / res are 16-bit tensors in HBM (ld* then count 16-bit elements) and
                           whether those are bf16 or fp16 (TTS_IO_F16; a 16-bit compute mode only takes its own format) */
-  const TtsTile* tiles; int32_t n_tiles; int32_t tile_rows; /* tts_conv1d_tile_rows() or the small form's 64 */
+  const TtsTile* tiles; int32_t n_tiles; int32_t tile_rows; /* tts_conv1d_tile_rows(), the small form's 64, or the wide form's 256 */
 } TtsConvDesc;
 
 /* BM (rows per tile) the conv kernel will use for this shape; build the tile table with it. */
@@ -114,6 +117,12 @@ int tts_conv1d_n_tile(int32_t cout, int32_t mode);
  * modes) may also run on 64 x 64 tiles - build the tile table with 64 rows and pass tile_rows = 64 to put ~3x more
  * workgroups on the chip when rows/128 * cols/n_tile would leave CUs idle - else 0. */
 int tts_conv1d_small_tile_rows(int32_t cout, int32_t mode, int32_t packed_cols);
+/* Wide form: build the tile table with 256 rows and pass tile_rows = 256 to run a plain 16-bit conv on 256 x 256 tiles fed by
+ * LDS-DMA (bit-identical to the other forms; faster once rows/256 * wn/256 fills the chip).  All of these must hold, else
+ * tts_conv1d returns TTS_E_ARG (it never falls back): compute bf16 or fp16; mode LINEAR; x, y and res (if any) 16-bit tensors in the
+ * call's own format; pre_act NONE; no seqvec, preadd or aux; cin == cin_pad and cin % 64 == 0; wn % 256 == 0; 16-byte aligned rows
+ * and pointers; 2 * (256 + (taps-1) dil) * 128 B + 66 KB of LDS within 160 KB.  (A shape whose regular tile is 256 rows itself -
+ * cout <= 32 - keeps that tile.) */
 int tts_conv1d(const TtsConvDesc* d, tts_stream_t stream);
 
 /*
