@@ -240,6 +240,15 @@ RESAMPLE_PROTOTYPES = {
 }
 RESAMPLE_MAX_FACTOR, RESAMPLE_LDS_TABLE_BYTES = 1024, 65536  # include/toucan_resample.h TTS_RESAMPLE_MAX_FACTOR, _LDS_TABLE_BYTES
 
+# symbol -> (restype, argtypes); mirrors include/toucan_prosody.h (per-utterance prosody scales: csrc/prosody.hip, stage entries in csrc/pipeline.hip)
+PROSODY_PROTOTYPES = {
+    "tts_prosody_control_v": (C.c_int, [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p]),
+    "tts_prosody_stats": (C.c_int, [_p, _p, _p, _p, _p, _i, _p, _p]),
+    "tts_control_and_regulate_v": (C.c_int, [_p, _p, _p, _p]),
+    "tts_copy_prosody_stats": (C.c_int, [_p, _p, _p, _p]),
+}
+PROSODY_SCALES, PROSODY_STATS = 4, 8  # include/toucan_prosody.h TTS_PROSODY_SCALES, TTS_PROSODY_STATS
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -263,7 +272,8 @@ def lib():
     handle = C.CDLL(LIB_PATH)
     _assert_single_hip_runtime()
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
-            list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()):
+            list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
+            list(PROSODY_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

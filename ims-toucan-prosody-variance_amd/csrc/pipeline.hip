@@ -6,6 +6,7 @@
 //   tts_encoder               Conformer.forward (Layers/Conformer.py:92-134) on the phoneme features
 //   tts_variance_predictors   VariancePredictor.forward / DurationPredictor.inference (VariancePredictor.py:65-80, DurationPredictor.py:63-83)
 //   tts_control_and_regulate  InferenceToucanTTS.py:214-235 (+ _scale_variance :333-343, LengthRegulator.py:37-61)
+//   tts_control_and_regulate_v  the same with per-utterance scales and the statistics around them (include/toucan_prosody.h)
 //   tts_teacher_forced        the scorer's replacement of the two above: ToucanTTS.py:321-330 (include/toucan_score.h)
 //   tts_decoder               decoder Conformer + feat_out (InferenceToucanTTS.py:238-239)
 //   tts_postnet               PostNet.forward + residual (PostNet.py:62-74, InferenceToucanTTS.py:241)
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "common.h"
+#include "../../include/toucan_prosody.h"
 #include "../../include/toucan_score.h"
 
 namespace tts {
@@ -200,6 +202,8 @@ struct Handle {
   int* dur = nullptr;
   float *cat = nullptr, *dec = nullptr, *mel0 = nullptr, *mel = nullptr;
   std::vector<int> frames;  // per utterance, after the control step
+  float* pstats = nullptr;           // [2][B][TTS_PROSODY_STATS] in the phoneme arena: before | after the scales (tts_control_and_regulate_v)
+  std::vector<float> pstats_host;    // the same, read back with the durations; empty if the batch went through the scalar entry
   bool have_flow = false;
   // profiling (bench.py's roofline leg): event pairs around the launches of the selected kernel class ("" = every class)
   bool prof_on = false, prof_detail = false;
@@ -786,7 +790,8 @@ size_t conformer_bytes(size_t R) { return R * (ATT * 4 * 4 + 1536 * 4 + 3 * ATT 
 
 // Arena sizes: ONE set of expressions for the stage entries (what they reserve) and for tts_workspace_bytes (what it promises).
 size_t phone_arena_bytes(size_t R, size_t B) {
-  return conformer_bytes(R) + R * (100 + 3 * ATT + 6 * 256 + 16) * 4 + B * (64 + 2 * ATT + 24 * 256 + 8) * 4 + (1 << 16);
+  return conformer_bytes(R) + R * (100 + 3 * ATT + 6 * 256 + 16) * 4 + B * (64 + 2 * ATT + 24 * 256 + 8) * 4 + (1 << 16) +
+         2 * B * TTS_PROSODY_STATS * 4 + 256;  // (the two statistics blocks of tts_control_and_regulate_v)
 }
 // cond_buffer: the PostFlow keeps the coupling blocks' conditioning [RS, 1536] in memory (every configuration but the 16-bit ones
 // with the fused WaveNet layer, which computes it inside the layer)
@@ -940,6 +945,8 @@ int pipeline_encoder(Handle* h, const float* text, const float* utt_emb, const i
   h->B = B;
   h->text = text;
   h->have_flow = false;
+  h->pstats = nullptr;
+  h->pstats_host.clear();
   const int R = h->lp.total;
   TTS_TRY(arena_reserve(h->phone, phone_arena_bytes(R, B), st));
   TTS_TRY(ensure_ptabs(h, st));
@@ -1078,6 +1085,45 @@ int pipeline_control_regulate(Handle* h, float duration_scale, float pitch_scale
   TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
   TTS_TRY(tts_prosody_control(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, h->B, duration_scale, pitch_scale, energy_scale, pause_scale, st));
   return regulate(h, h->dur, false, frames_out, st);
+}
+
+// ---- stage A.3 / B.0 with per-utterance scales (include/toucan_prosody.h) ------------------------------------------------------
+// overrides -> statistics -> scales -> statistics, then regulate(): its duration read-back is the one host round trip, and the
+// statistics ride on it (their copy is enqueued in front of it).  scales: host [B][4]; they go up through the table store of the
+// acoustic stages (pinned staging, one asynchronous copy on st; a batch that repeats a table of scales finds it there).
+int pipeline_control_regulate_v(Handle* h, const float* scales, int* frames_out, hipStream_t st) {
+  TTS_CHECK_ARG(h && h->enc && h->dur, "tts_control_and_regulate_v: run tts_encoder and tts_variance_predictors first");
+  TTS_CHECK_ARG(scales, "tts_control_and_regulate_v: null scales");
+  const int B = h->B;
+  for (int u = 0; u < B; ++u) {
+    const float ds = scales[(size_t)u * TTS_PROSODY_SCALES];
+    TTS_CHECK_ARG(std::isfinite(ds) && ds > 0.f, "tts_control_and_regulate_v: utterance %d: duration_scaling_factor %g must be positive and finite",
+                  u, (double)ds);
+  }
+  TTS_CHECK_RESOLVED(h, "tts_control_and_regulate_v");
+  h->tab_which = 0;
+  const int *pb, *pe;
+  TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
+  // (a layout key is 4 (2 n + 1) bytes long, this one 14 + 16 B: the two kinds never collide)
+  std::string key("prosody_scales");
+  key.append(reinterpret_cast<const char*>(scales), (size_t)B * TTS_PROSODY_SCALES * sizeof(float));
+  void* sdev;
+  TTS_TRY(table_of(h, key, st, [&] { return std::vector<float>(scales, scales + (size_t)B * TTS_PROSODY_SCALES); }, &sdev, nullptr));
+  const size_t NS = (size_t)B * TTS_PROSODY_STATS;
+  if (!h->pstats) {
+    TTS_ALLOC(ps, h->phone, float, 2 * NS);
+    h->pstats = ps;
+  }
+  float *before = h->pstats, *after = h->pstats + NS;
+  TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, nullptr, st));
+  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, before, st));
+  TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, static_cast<const float*>(sdev), st));
+  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, after, st));
+  h->pstats_host.assign(2 * NS, 0.f);
+  TTS_TRY(hip_ok(hipMemcpyAsync(h->pstats_host.data(), h->pstats, 2 * NS * sizeof(float), hipMemcpyDeviceToHost, st), "prosody statistics to host"));
+  const int rc = regulate(h, h->dur, false, frames_out, st);  // (synchronises st once: the durations and the statistics are on the host)
+  if (rc != TTS_OK) h->pstats_host.clear();
+  return rc;
 }
 
 // ---- stage A.2 + A.3 with teacher forcing (the scorer): raw predictions, gold prosody, gold durations -----------------------
@@ -1519,6 +1565,21 @@ int tts_control_and_regulate(TtsHandle* h, float duration_scale, float pitch_sca
                              int32_t* frame_counts, tts_stream_t stream) {
   return tts::stage_done(H(h), 0, ST(stream),
                          tts::pipeline_control_regulate(H(h), duration_scale, pitch_scale, energy_scale, pause_scale, frame_counts, ST(stream)));
+}
+int tts_control_and_regulate_v(TtsHandle* h, const float* scales, int32_t* frame_counts, tts_stream_t stream) {
+  return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_control_regulate_v(H(h), scales, frame_counts, ST(stream)));
+}
+int tts_copy_prosody_stats(TtsHandle* h, float* before, float* after, tts_stream_t stream) {
+  (void)stream;  // (the blocks came back with the durations: a host copy)
+  tts::Handle* hh = H(h);
+  if (!hh || hh->pstats_host.empty()) {
+    tts::set_error("tts_copy_prosody_stats: the batch in flight did not go through tts_control_and_regulate_v");
+    return TTS_E_ARG;
+  }
+  const size_t n = (size_t)hh->B * TTS_PROSODY_STATS;
+  if (before) memcpy(before, hh->pstats_host.data(), n * sizeof(float));
+  if (after) memcpy(after, hh->pstats_host.data() + n, n * sizeof(float));
+  return TTS_OK;
 }
 int tts_teacher_forced(TtsHandle* h, const float* gold_pitch, const float* gold_energy, const int32_t* gold_durations, float* pred_log_dur,
                        float* pred_pitch, float* pred_energy, int32_t* frame_counts, tts_stream_t stream) {

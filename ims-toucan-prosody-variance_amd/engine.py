@@ -13,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from . import capi, packing
+from . import capi, packing, prosody
 from .capi import (ACT_NONE, ACT_RELU, ACT_TANH, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32, COMPUTE_F32X3, MODE_COUPLING, MODE_GATED, MODE_GLU,
                    MODE_LINEAR, PRE_LRELU, PRE_NONE, PRE_SNAKE)
 from .ragged import Ragged
@@ -296,6 +296,19 @@ class Ops:
         capi.check(self.lib.tts_prosody_control(text.data_ptr(), _ld(text), pitch.data_ptr(), energy.data_ptr(), dur.data_ptr(),
                                                 sb.data_ptr(), se.data_ptr(), rag.n_seq, duration_scale, pitch_scale, energy_scale,
                                                 pause_scale, self.stream()), "tts_prosody_control")
+
+    def prosody_control_v(self, text, pitch, energy, dur, rag, scales):
+        """tts_prosody_control with the four scales of every utterance from ``scales`` ([n_seq, 4] float32 on the device); None: the
+        linguistic overrides alone (include/toucan_prosody.h)."""
+        sb, se = rag.bounds()
+        capi.check(self.lib.tts_prosody_control_v(text.data_ptr(), _ld(text), pitch.data_ptr(), energy.data_ptr(), dur.data_ptr(),
+                                                  sb.data_ptr(), se.data_ptr(), rag.n_seq, _ptr(scales), self.stream()), "tts_prosody_control_v")
+
+    def prosody_stats(self, pitch, energy, dur, rag, stats):
+        sb, se = rag.bounds()
+        capi.check(self.lib.tts_prosody_stats(pitch.data_ptr(), energy.data_ptr(), dur.data_ptr(), sb.data_ptr(), se.data_ptr(), rag.n_seq,
+                                              stats.data_ptr(), self.stream()), "tts_prosody_stats")
+        return stats
 
     def length_regulate(self, enc, pitch, energy, wp, bp, we, be, dur, rag_phone, rag_frame, up, dec_in, dec_scale):
         pb, pe = rag_phone.bounds()
@@ -637,6 +650,13 @@ class AcousticEngine:
             d.copy_(gold_d)
         if taps is not None:
             taps.update(enc_out=enc.clone(), pitch_raw=p.clone(), energy_raw=en.clone())
+        if torch.is_tensor(scales):  # per-utterance scales [B, 4]: overrides -> statistics -> scales -> statistics
+            stats = ops.empty(2, B, capi.PROSODY_STATS)
+            ops.prosody_control_v(text, p, en, d, rag_p, None)
+            ops.prosody_stats(p, en, d, rag_p, stats[0])
+            ops.prosody_control_v(text, p, en, d, rag_p, scales)
+            ops.prosody_stats(p, en, d, rag_p, stats[1])
+            return enc, p, en, d, stats
         ops.prosody_control(text, p, en, d, rag_p, *scales)
         return enc, p, en, d
 
@@ -675,6 +695,8 @@ class AcousticEngine:
                 pause_duration_scaling_factor=1.0, run_postflow=True, taps=None, generator=None):
         """texts: list of [L_u,62] float tensors; utt_embs: [B,64]; lang_ids: list of int or None;
         durations/pitch/energy: optional lists (gold values, InferenceToucanTTS.py:209-211);
+        the four scales: a scalar for the batch, or one value per utterance (any sequence takes the per-utterance kernels and adds
+        ``prosody_stats`` = (before, after), float32 [B, 8] arrays with the columns prosody.STATS, to the result);
         z_noise: optional list of [80, T_u] tensors = 0.8*N(0,1) (Glow.py:363) - drawn on the device if omitted.
         Returns dict(mel=[list of [T'_u,80]], durations, pitch, energy, plus packed tensors).
 
@@ -687,7 +709,8 @@ class AcousticEngine:
                                     pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor, run_postflow, taps, generator)
         ops, dev = self.ops, self.device
         B = len(texts)
-        assert duration_scaling_factor > 0
+        table = prosody.resolve_scales(B, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor)
+        assert table is not None or duration_scaling_factor > 0
         Ls = [int(t.shape[0]) for t in texts]
         rag_p = Ragged.cached(Ls, dev)
         rag_b = Ragged.cached([B], dev)
@@ -701,16 +724,25 @@ class AcousticEngine:
         if self.multilingual and lang_ids is not None:
             lang_idx = torch.tensor([int(i) for i in lang_ids], dtype=torch.int32).to(dev)
         gp, ge, gd = packed_gold(pitch, torch.float32), packed_gold(energy, torch.float32), packed_gold(durations, torch.int32)
-        scales = (float(duration_scaling_factor), float(pitch_variance_scale), float(energy_variance_scale),
-                  float(pause_duration_scaling_factor))
         graphs = self.use_graphs and taps is None and dev.type == "cuda"
-
-        if graphs:
-            key = ("A", tuple(Ls), lang_idx is not None, gp is not None, ge is not None, gd is not None, scales)
-            ins = dict(text=text, emb=emb, lang_idx=lang_idx, gold_p=gp, gold_e=ge, gold_d=gd)
-            enc, p, en, d = self._graphs.run(key, ins, lambda **kw: self._stage_a(rag_p=rag_p, rag_b=rag_b, scales=scales, **kw))
+        stats = None
+        if table is not None:  # per-utterance scales: a device table, an input of the captured graph like the text
+            scales = torch.from_numpy(table).to(dev)
+            if graphs:
+                key = ("A", tuple(Ls), lang_idx is not None, gp is not None, ge is not None, gd is not None, "per-utterance scales")
+                ins = dict(text=text, emb=emb, lang_idx=lang_idx, gold_p=gp, gold_e=ge, gold_d=gd, scales=scales)
+                enc, p, en, d, stats = self._graphs.run(key, ins, lambda **kw: self._stage_a(rag_p=rag_p, rag_b=rag_b, **kw))
+            else:
+                enc, p, en, d, stats = self._stage_a(text, emb, lang_idx, gp, ge, gd, rag_p, rag_b, scales, taps)
         else:
-            enc, p, en, d = self._stage_a(text, emb, lang_idx, gp, ge, gd, rag_p, rag_b, scales, taps)
+            scales = (float(duration_scaling_factor), float(pitch_variance_scale), float(energy_variance_scale),
+                      float(pause_duration_scaling_factor))
+            if graphs:
+                key = ("A", tuple(Ls), lang_idx is not None, gp is not None, ge is not None, gd is not None, scales)
+                ins = dict(text=text, emb=emb, lang_idx=lang_idx, gold_p=gp, gold_e=ge, gold_d=gd)
+                enc, p, en, d = self._graphs.run(key, ins, lambda **kw: self._stage_a(rag_p=rag_p, rag_b=rag_b, scales=scales, **kw))
+            else:
+                enc, p, en, d = self._stage_a(text, emb, lang_idx, gp, ge, gd, rag_p, rag_b, scales, taps)
 
         # ---- the one host round trip: frame counts fix every later buffer size ----
         d_host = d.cpu().numpy()
@@ -745,6 +777,9 @@ class AcousticEngine:
         out["durations"] = [d[b0:b0 + n] for b0, n in zip(rag_p.begins, rag_p.lengths)]
         out["pitch"] = [p[b0:b0 + n] for b0, n in zip(rag_p.begins, rag_p.lengths)]
         out["energy"] = [en[b0:b0 + n] for b0, n in zip(rag_p.begins, rag_p.lengths)]
+        if stats is not None:
+            stats = stats.cpu().numpy()
+            out["prosody_stats"] = (stats[0], stats[1])
         return out
 
     @torch.inference_mode()

@@ -9,7 +9,9 @@ script written against the reference (run_text_to_file_reader.py:8-16) works unc
   (run_weight_averaging.py:108-116); weight norm folding / flow inverses happen in ``packing.py``
 * ``forward`` / ``__call__`` (:132-229), ``read_to_file`` (:231-285: 10 600 samples of silence around sentences, blank
   strings skipped, 24 kHz output or sample-doubled 48 kHz PCM16), ``read_aloud`` (:287-309), the language / embedding setters
-* additive API: ``synthesize_batch`` (ragged batches, optionally sharded over the ranks of torch.distributed)
+* additive API: ``synthesize_batch`` (ragged batches, optionally sharded over the ranks of torch.distributed; every prosody scale
+  a scalar or one value per utterance), ``synthesize_grid`` (one text over a grid of prosody scales, with the statistics of what
+  each scale did)
 
 * ``set_utterance_embedding(path)`` (:103-114): reference audio -> log-mel -> GST style embedding on the GPU (style.py)
 
@@ -22,7 +24,7 @@ import wave as _wave
 import numpy as np
 import torch
 
-from . import engine
+from . import engine, prosody
 from .phonemes import ArticulatoryCombinedTextFrontend, get_language_id
 from .ragged import Ragged
 
@@ -156,6 +158,7 @@ class ToucanTTSInterface(torch.nn.Module):
 
         self.embedding_model_path = embedding_model_path  # GST network: loaded on the first set_utterance_embedding(path)
         self._style = None
+        self.last_prosody_stats = None  # (before, after) of the last batch that took per-utterance prosody scales
 
 
         self.default_utterance_embedding = checkpoint["default_emb"].to(self.device)
@@ -247,11 +250,13 @@ class ToucanTTSInterface(torch.nn.Module):
             out = self.pipe.forward(phones, emb, lang_ids, z_noise=z_noise, **kw)
             self.last_durations, self.last_pitch, self.last_energy = out["durations"], out["pitch"], out["energy"]
             self.last_mel = out["mel"]
+            self.last_prosody_stats = out.get("prosody_stats")
             return out["wav"], out["wav_spans"]
         out = self.phone2mel.forward(phones, emb, lang_ids, z_noise=z_noise, **kw)
         wav, rag = self.mel2wav.forward(out["mel_packed"], out["rag_mel"])
         self.last_durations, self.last_pitch, self.last_energy = out["durations"], out["pitch"], out["energy"]
         self.last_mel = out["mel"]
+        self.last_prosody_stats = out.get("prosody_stats")
         return wav, list(zip(rag.begins, rag.lengths))
 
     def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, **kw):
@@ -297,10 +302,20 @@ class ToucanTTSInterface(torch.nn.Module):
         texts: phoneme strings (or [L,62] feature tensors).  durations / pitch / energy: optional per-utterance gold prosody (the
         cloner-style call, UtteranceCloner.py:163).  With ``distributed=True`` and an initialised process group the utterances are
         dealt over the ranks by frame count and every rank returns all waveforms (distributed.py).  ``sample_rate`` / ``pcm16``:
-        the waveforms at another rate than 24 kHz and / or as int16, converted on the device (not with ``distributed=True``)."""
+        the waveforms at another rate than 24 kHz and / or as int16, converted on the device (not with ``distributed=True``).
+        The four prosody scales: each a scalar for the batch or a sequence with one value per utterance.  Any sequence takes the
+        per-utterance kernels - an utterance still equals the call on it alone with its own scalars - and leaves
+        ``self.last_prosody_stats`` = (before, after): float32 [B, 8] arrays (columns ``prosody.STATS``) of every utterance's pitch /
+        energy / durations before and after its scales; an all-scalar call leaves None there.  ValueError for a sequence of the
+        wrong length, a duration factor that is not positive (the message names the utterance), and sequences with
+        ``distributed=True`` (the sharded deal does not carry them)."""
         if distributed and (sample_rate is not None or pcm16):
             raise ValueError("sample_rate / pcm16 are not available with distributed=True: the sharded exchange carries 24 kHz float32")
         self._check_output_format(sample_rate, pcm16)
+        per_utterance = prosody.resolve_scales(len(texts), duration_scaling_factor, pitch_variance_scale, energy_variance_scale,
+                                               pause_duration_scaling_factor) is not None
+        if distributed and per_utterance:
+            raise ValueError("per-utterance prosody scales are not available with distributed=True: the sharded deal carries scalars")
         feats = [t if torch.is_tensor(t) else self.text2phone.string_to_tensor(t, input_phonemes=input_is_phones) for t in texts]
         embs = utterance_embeddings if utterance_embeddings is not None else [self.default_utterance_embedding] * len(feats)
         kw = dict(duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
@@ -328,6 +343,42 @@ class ToucanTTSInterface(torch.nn.Module):
             return mean
         wav, spans = self._convert(mean, [(0, m)], sample_rate, pcm16)
         return wav[spans[0][0]:spans[0][0] + spans[0][1]]
+
+    def synthesize_grid(self, text, duration_scaling_factors=(1.0,), pitch_variance_scales=(1.0,), energy_variance_scales=(1.0,),
+                        pause_duration_scaling_factors=(1.0,), input_is_phones=True, utterance_embedding=None, durations=None, pitch=None,
+                        energy=None, z_noise=None, sample_rate=None, pcm16=False):
+        """Additive API: ONE text (a phoneme string, or its [L, 62] feature tensor) at every combination of the four tuples of prosody scales - the Cartesian product in row-major
+        order of the tuples as listed (the pause factor varies fastest) - synthesised as ragged batches of at most MAX_FILE_BATCH
+        variants with per-utterance scales instead of one pass per setting.  Returns one dict per variant, in that order:
+        ``scales`` (duration, pitch, energy, pause), ``wave``, ``frames`` (mel frames of the wave), ``stats_before`` /
+        ``stats_after`` (float32 [8], columns ``prosody.STATS``: the variant's pitch / energy / durations after the linguistic
+        overrides, before and after its scales - their ratio is what a scale really did, the reference's clamp at 0 and its shift of
+        the zeros included).  Every variant equals ``forward`` of the text with its four scalars.  durations / pitch / energy: gold
+        prosody of the text, shared by the variants; ``z_noise``: None or one [80, T] entry per variant; ``sample_rate`` / ``pcm16`` as
+        in ``forward``.  The variants are replicated on the host: every one runs the whole model."""
+        self._check_output_format(sample_rate, pcm16)
+        variants = prosody.grid(duration_scaling_factors, pitch_variance_scales, energy_variance_scales, pause_duration_scaling_factors)
+        if z_noise is not None and len(z_noise) != len(variants):
+            raise ValueError(f"z_noise holds {len(z_noise)} entries, the grid has {len(variants)} variants")
+        prosody.resolve_scales(len(variants), *[[v[k] for v in variants] for k in range(4)])  # (the duration factors, before anything runs)
+        emb = self.default_utterance_embedding if utterance_embedding is None else utterance_embedding
+        results = []
+        with torch.inference_mode():
+            phones = text if torch.is_tensor(text) else self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
+            for lo in range(0, len(variants), self.MAX_FILE_BATCH):
+                chunk = variants[lo:lo + self.MAX_FILE_BATCH]
+                n = len(chunk)
+                rep = lambda v: None if v is None else [v] * n
+                wav24, spans24 = self._synthesize_packed([phones] * n, [emb] * n, [self._lang()] * n,
+                                                         z_noise=None if z_noise is None else list(z_noise[lo:lo + n]),
+                                                         durations=rep(durations), pitch=rep(pitch), energy=rep(energy),
+                                                         **{name: [v[k] for v in chunk] for k, name in enumerate(prosody.KNOBS)})
+                before, after = self.last_prosody_stats
+                wav, spans = self._convert(wav24, spans24, sample_rate, pcm16)
+                for i, scales in enumerate(chunk):
+                    results.append({"scales": scales, "wave": wav[spans[i][0]:spans[i][0] + spans[i][1]], "frames": int(spans24[i][1]) // 384,
+                                    "stats_before": before[i], "stats_after": after[i]})
+        return results
 
     def stream(self, text, input_is_phones=False, chunk_frames=512, halo_frames=None, max_batch=4, z_noise=None, sample_rate=None, pcm16=False, **prosody):
         """Generator of waveform pieces for ONE (long) text: the acoustic model runs once, the vocoder chunk-wise with overlap

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import capi, engine, packing
+from . import capi, engine, packing, prosody
 from .ragged import Ragged
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 4}
@@ -49,6 +49,7 @@ class NativePipeline:
         voc = None
         self.kind = vocoder_kind
         self._streams = None  # (acoustic, vocoder) stream pair of forward_pipelined, made on first use
+        self._prosody_stats = None  # (before, after) of the last stage A that took per-utterance scales
         if vocoder_sd is not None:
             assert vocoder_kind in ("hifigan", "bigvgan")
             voc = engine.VocoderEngine(vocoder_sd, vocoder_kind, "cpu", precision=self.vocoder_precision, pack_only=True)
@@ -281,15 +282,25 @@ class NativePipeline:
         return z_sq
 
     def _stage_a(self, packed, duration_scale, pitch_scale, energy_scale, pause_scale, st):
-        """Stage A on a packed batch (tts_encoder, tts_variance_predictors, tts_control_and_regulate): mel frames per utterance."""
+        """Stage A on a packed batch (tts_encoder, tts_variance_predictors, tts_control_and_regulate - or its _v form when a scale is a
+        sequence: one value per utterance, scalars among them broadcast): mel frames per utterance."""
         lib, Ls = self.lib, packed["Ls"]
         B = len(Ls)
+        table = prosody.resolve_scales(B, duration_scale, pitch_scale, energy_scale, pause_scale)  # (ValueError before anything is enqueued)
         self._ensure_pe(max(Ls))
         capi.check(lib.tts_encoder(self.h, ptr(packed["text"]), ptr(packed["emb"]), ptr(packed["lang"]), (C.c_int32 * B)(*Ls), B, st), "tts_encoder")
         capi.check(lib.tts_variance_predictors(self.h, ptr(packed["gp"]), ptr(packed["ge"]), ptr(packed["gd"]), st), "tts_variance_predictors")
         frames = (C.c_int32 * B)()
-        capi.check(lib.tts_control_and_regulate(self.h, float(duration_scale), float(pitch_scale), float(energy_scale), float(pause_scale), frames, st),
-                   "tts_control_and_regulate")
+        self._prosody_stats = None
+        if table is None:
+            capi.check(lib.tts_control_and_regulate(self.h, float(duration_scale), float(pitch_scale), float(energy_scale), float(pause_scale), frames, st),
+                       "tts_control_and_regulate")
+            return [int(f) for f in frames]
+        # per-utterance scales (include/toucan_prosody.h): the statistics come back with the durations, inside the entry's one round trip
+        capi.check(lib.tts_control_and_regulate_v(self.h, table.ctypes.data_as(C.c_void_p), frames, st), "tts_control_and_regulate_v")
+        before, after = (np.empty((B, capi.PROSODY_STATS), dtype=np.float32) for _ in range(2))
+        capi.check(lib.tts_copy_prosody_stats(self.h, before.ctypes.data_as(C.c_void_p), after.ctypes.data_as(C.c_void_p), st), "tts_copy_prosody_stats")
+        self._prosody_stats = (before, after)
         return [int(f) for f in frames]
 
     @torch.inference_mode()
@@ -297,13 +308,13 @@ class NativePipeline:
                 pitch_variance_scale=1.0, energy_variance_scale=1.0, pause_duration_scaling_factor=1.0, run_postflow=True, vocode=True,
                 generator=None, packed=None, z_sq=None):
         """Same arguments and result keys as engine.AcousticEngine.forward (+ ``wav`` / ``wav_spans`` when a vocoder is loaded and
-        ``vocode``).  Every stage is one call into libtoucan_hip.so."""
+        ``vocode``; ``prosody_stats`` when a scale is a sequence).  Every stage is one call into libtoucan_hip.so."""
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
                 return self.forward(texts, utt_embs, lang_ids, durations, pitch, energy, z_noise, duration_scaling_factor, pitch_variance_scale,
                                     energy_variance_scale, pause_duration_scaling_factor, run_postflow, vocode, generator, packed, z_sq)
         dev, lib, st = self.device, self.lib, self._stream()
-        assert duration_scaling_factor > 0
+        assert np.ndim(duration_scaling_factor) > 0 or duration_scaling_factor > 0  # (a sequence is checked per utterance in _stage_a)
         if packed is None:
             packed = self.pack_inputs(texts, utt_embs, lang_ids, durations, pitch, energy)
         Ls = packed["Ls"]
@@ -337,6 +348,8 @@ class NativePipeline:
         en = torch.empty(R, dtype=torch.float32, device=dev)
         capi.check(lib.tts_copy_prosody(self.h, ptr(d), ptr(p), ptr(en), st), "tts_copy_prosody")
         out = dict(durations_packed=d, pitch_packed=p, energy_packed=en, rag_phone=rag_p, rag_frame=rag_f, mel_packed=mel_packed, rag_mel=rag_out)
+        if self._prosody_stats is not None:
+            out["prosody_stats"] = self._prosody_stats
         out["mel"] = [mel_packed[b0:b0 + n] for b0, n in zip(rag_out.begins, rag_out.lengths)]
         for key, src in (("durations", d), ("pitch", p), ("energy", en)):
             out[key] = [src[b0:b0 + n] for b0, n in zip(rag_p.begins, rag_p.lengths)]
