@@ -73,6 +73,7 @@ __device__ __forceinline__ float bf16_to_f32(unsigned short u) { return __builti
 // round-to-nearest-even, two values per instruction (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).  fp16 does not saturate: the
 // callers keep everything that can leave its range (flow state, norm statistics, accumulators) in fp32.
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned short f32_to_f16(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
@@ -87,15 +88,13 @@ __device__ __forceinline__ float from16(unsigned short u) {
   if constexpr (F16) return f16_to_f32(u);
   else return bf16_to_f32(u);
 }
-// (lo, hi) -> one dword of two 16-bit elements
+// (lo, hi) -> one dword of two 16-bit elements: one packed conversion either way (converted one by one and or-ed together, the
+// bf16 pair cost two conversions, a shift and an or)
 template <bool F16>
 __device__ __forceinline__ unsigned int pack16(float lo, float hi) {
-  if constexpr (F16) {
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, f16x2));
-  } else {
-    return (unsigned int)f32_to_bf16(lo) | ((unsigned int)f32_to_bf16(hi) << 16);
-  }
+  const f32x2 v = {lo, hi};
+  if constexpr (F16) return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, f16x2));
+  else return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
 }
 // run-time format (tensors in HBM whose format is a flag of the call, TTS_IO_F16)
 __device__ __forceinline__ float load16(unsigned short u, bool f16) { return f16 ? f16_to_f32(u) : bf16_to_f32(u); }

@@ -359,31 +359,46 @@ __global__ __launch_bounds__(RbCfg<C>::THREADS, (C == 32 ? RB_C32_WAVES : (C == 
   constexpr bool XPF = MFIR && IOB && C == 128;
   const int img_units = img_rows * Q8;
   uint4 xv[PERX], xv2[(MFIR && !IOB) ? PERX : 1];
+  // A thread's units of one round: THREADS is a multiple of Q8, so its channel group (base % Q8) never changes and its image row
+  // advances by RPU per unit - row and column are split once per round, and every unit's row is a constant apart.
+  // Loads: the image row's frame, clamped into the utterance (any row is then a valid address: no bound on the unit index),
+  // as a 32-bit offset from the tile's first fetched row, which is wave-uniform (scalar base + vector offset addressing).
+  // Stores: ONE predicate per unit - the image rows [live_lo, live_lo + live_n) are frames of the utterance inside the window,
+  // every other row is zeros (the reference zero-pads per utterance; the surplus rows behind the window only meet zero taps).
+  constexpr int RPU = RB_THREADS / Q8;
+  static_assert(RB_THREADS % Q8 == 0 && (Q8 & (Q8 - 1)) == 0, "a thread keeps its channel group across units");
   auto stage_issue = [&](const TtsTile& tl, int base) __attribute__((always_inline)) {
     const int Tn = tl.seq_end - tl.seq_begin, fr0 = tl.row0 - tl.seq_begin - RB_LEAD - h1 - PADR;
+    const int t_lo = fr0 < 0 ? 0 : (fr0 > Tn - 1 ? Tn - 1 : fr0);  // first frame any unit fetches (wave-uniform)
+    const int rel = fr0 - t_lo, rel_max = Tn - 1 - t_lo;
+    const int r0 = (int)((unsigned)base / Q8) + rel;
+    const unsigned int c8 = ((unsigned)base % Q8) * 8;
+    const char* src = IOB ? reinterpret_cast<const char*>(xh + (size_t)(tl.seq_begin + t_lo) * d.ldx)
+                          : reinterpret_cast<const char*>(d.x + (size_t)(tl.seq_begin + t_lo) * d.ldx);
 #pragma unroll
     for (int p = 0; p < PERX; ++p) {
-      int e = base + p * RB_THREADS;
-      e = e < img_units ? e : img_units - 1;
-      const int r = e / Q8, c8 = (e % Q8) * 8;
-      const int t = fr0 + r;
-      const int tc = t < 0 ? 0 : (t > Tn - 1 ? Tn - 1 : t);  // (rows outside the utterance are zeroed when they are stored)
+      int tr = r0 + p * RPU;  // frame of the unit's row, relative to t_lo
+      tr = tr < 0 ? 0 : (tr > rel_max ? rel_max : tr);
+      const unsigned int off = __umul24((unsigned)tr, (unsigned)d.ldx) + c8;  // (rows of one image x ldx: checked on the host)
       if constexpr (IOB) {
-        xv[p] = *reinterpret_cast<const uint4*>(xh + (size_t)(tl.seq_begin + tc) * d.ldx + c8);
+        xv[p] = *reinterpret_cast<const uint4*>(src + off * 2u);
       } else {
-        xv[p] = *reinterpret_cast<const uint4*>(d.x + (size_t)(tl.seq_begin + tc) * d.ldx + c8);
-        xv2[p] = *reinterpret_cast<const uint4*>(d.x + (size_t)(tl.seq_begin + tc) * d.ldx + c8 + 4);
+        xv[p] = *reinterpret_cast<const uint4*>(src + off * 4u);
+        xv2[p] = *reinterpret_cast<const uint4*>(src + off * 4u + 16u);
       }
     }
   };
   auto stage_commit = [&](const TtsTile& tl, int base) __attribute__((always_inline)) {
     const int Tn = tl.seq_end - tl.seq_begin, fr0 = tl.row0 - tl.seq_begin - RB_LEAD - h1 - PADR;
+    const int live_lo = fr0 < 0 ? -fr0 : 0;
+    const int live_hi = Tn - fr0 < win_rows + 2 * PADR ? Tn - fr0 : win_rows + 2 * PADR;
+    const unsigned int live_n = live_hi > live_lo ? (unsigned)(live_hi - live_lo) : 0u;
+    const int r0 = (int)((unsigned)base / Q8);
+    unsigned short* dst = img + r0 * XP + (int)(((unsigned)base % Q8) * 8);
 #pragma unroll
     for (int p = 0; p < PERX; ++p) {
-      const int e = base + p * RB_THREADS;
-      if (e >= img_units) continue;
-      const int r = e / Q8, c8 = (e % Q8) * 8;
-      const int t = fr0 + r;
+      const int r = r0 + p * RPU;
+      if (r >= img_rows) continue;
       uint4 o;
       if constexpr (IOB && F16) {
         o = xv[p];
@@ -391,16 +406,15 @@ __global__ __launch_bounds__(RbCfg<C>::THREADS, (C == 32 ? RB_C32_WAVES : (C == 
         const unsigned int w4[4] = {xv[p].x, xv[p].y, xv[p].z, xv[p].w};
         unsigned int o4[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) o4[q] = pack16<true>(bf16_to_f32(w4[q] & 0xFFFF), bf16_to_f32(w4[q] >> 16));
+        for (int q = 0; q < 4; ++q) o4[q] = pack16<true>(__builtin_bit_cast(float, w4[q] << 16), __builtin_bit_cast(float, w4[q] & 0xFFFF0000u));
         o = make_uint4(o4[0], o4[1], o4[2], o4[3]);
       } else {
         auto fb = [](unsigned int b) { return __builtin_bit_cast(float, b); };
         o = make_uint4(pack16<true>(fb(xv[p].x), fb(xv[p].y)), pack16<true>(fb(xv[p].z), fb(xv[p].w)),
                        pack16<true>(fb(xv2[p].x), fb(xv2[p].y)), pack16<true>(fb(xv2[p].z), fb(xv2[p].w)));
       }
-      // frames outside the utterance and the surplus rows behind the window: zeros
-      if (t < 0 || t >= Tn || r >= win_rows + 2 * PADR) o = make_uint4(0, 0, 0, 0);
-      *reinterpret_cast<uint4*>(img + r * XP + c8) = o;
+      if (!((unsigned)(r - live_lo) < live_n)) o = make_uint4(0, 0, 0, 0);
+      *reinterpret_cast<uint4*>(dst + p * RPU * XP) = o;
     }
   };
   if (tid == 0) {
@@ -545,63 +559,56 @@ __global__ __launch_bounds__(RbCfg<C>::THREADS, (C == 32 ? RB_C32_WAVES : (C == 
           for (int i = 0; i < GR; ++i) xa[(wr0 + i) * XP + chl] = 0;
         }
       }
-    } else if constexpr (IOB) {
-      // bf16 input: 8 channels per 16-byte load; PER loads in flight per thread (clamped addresses, no branches)
-      constexpr int Q8 = KC / 8, PER = 4;
-      const int total = win_rows * Q8;
+    } else {
+      // LeakyReLU while staging: 16-byte units (8 channels of 16-bit x, 4 of fp32 x), PER independent loads per thread in flight
+      // before the first one is consumed.  Indexed as the snake's image is (see stage_issue): row and channel group split once
+      // per round, a constant row step per unit, frames clamped into the utterance (so no load needs a bound or a branch), 32-bit
+      // offsets from the window's first fetched row, and one predicate per unit for "a frame of the utterance"
+      constexpr int QU = IOB ? KC / 8 : KC / 4, EPU = IOB ? 8 : 4, PER = 4, RPU = RB_THREADS / QU;
+      static_assert(RB_THREADS % QU == 0 && (QU & (QU - 1)) == 0, "a thread keeps its channel group across units");
+      const int total = win_rows * QU;
+      const int t_lo = wbase < 0 ? 0 : (wbase > T - 1 ? T - 1 : wbase);
+      const int rel = wbase - t_lo, rel_max = T - 1 - t_lo;
+      const int live_lo = wbase < 0 ? -wbase : 0, live_hi = T - wbase < win_rows ? T - wbase : win_rows;
+      const unsigned int live_n = live_hi > live_lo ? (unsigned)(live_hi - live_lo) : 0u;
+      const char* src = IOB ? reinterpret_cast<const char*>(xh + (size_t)(tile.seq_begin + t_lo) * d.ldx + c0)
+                            : reinterpret_cast<const char*>(d.x + (size_t)(tile.seq_begin + t_lo) * d.ldx + c0);
       for (int base = tid; base < total; base += RB_THREADS * PER) {
+        const int r0 = (int)((unsigned)base / QU);
+        const unsigned int cu = ((unsigned)base % QU) * EPU;
         uint4 v[PER];
 #pragma unroll
         for (int p = 0; p < PER; ++p) {
-          int e = base + p * RB_THREADS;
-          e = e < total ? e : total - 1;
-          const int wr = e / Q8, c8 = (e % Q8) * 8;
-          const int t = wbase + wr;
-          const int tc = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
-          v[p] = *reinterpret_cast<const uint4*>(xh + (size_t)(tile.seq_begin + tc) * d.ldx + c0 + c8);
-          if (t < 0 || t >= T) v[p] = make_uint4(0, 0, 0, 0);
+          int tr = r0 + rel + p * RPU;
+          tr = tr < 0 ? 0 : (tr > rel_max ? rel_max : tr);
+          v[p] = *reinterpret_cast<const uint4*>(src + (__umul24((unsigned)tr, (unsigned)d.ldx) + cu) * (IOB ? 2u : 4u));
         }
+        unsigned short* dst = xa + r0 * XP + (int)cu;
 #pragma unroll
         for (int p = 0; p < PER; ++p) {
-          int e = base + p * RB_THREADS;
-          e = e < total ? e : total - 1;
-          const int wr = e / Q8, c8 = (e % Q8) * 8;
+          const int wr = r0 + p * RPU;
+          if (wr >= win_rows) continue;
+          const bool in = (unsigned)(wr - live_lo) < live_n;
           const unsigned int w4[4] = {v[p].x, v[p].y, v[p].z, v[p].w};
-          unsigned int o4[4];
+          if constexpr (IOB) {
+            unsigned int o4[4];
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float lo = from16<F16>(w4[q] & 0xFFFF), hi2 = from16<F16>(w4[q] >> 16);
-            lo = lo > 0.f ? lo : lo * d.slope;
-            hi2 = hi2 > 0.f ? hi2 : hi2 * d.slope;
-            o4[q] = pack16<F16>(lo, hi2);
+            for (int q = 0; q < 4; ++q) {
+              float lo = from16<F16>(w4[q] & 0xFFFF), hi2 = from16<F16>(w4[q] >> 16);
+              lo = lo > 0.f ? lo : lo * d.slope;
+              hi2 = hi2 > 0.f ? hi2 : hi2 * d.slope;
+              o4[q] = in ? pack16<F16>(lo, hi2) : 0u;
+            }
+            *reinterpret_cast<uint4*>(dst + p * RPU * XP) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+          } else {
+            float f4[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const float xq = __builtin_bit_cast(float, w4[q]);
+              f4[q] = xq > 0.f ? xq : xq * d.slope;
+            }
+            *reinterpret_cast<uint2*>(dst + p * RPU * XP) = in ? make_uint2(pack16<F16>(f4[0], f4[1]), pack16<F16>(f4[2], f4[3])) : make_uint2(0u, 0u);
           }
-          *reinterpret_cast<uint4*>(xa + wr * XP + c8) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
-        }
-      }
-    } else {
-      // PER independent 16-byte loads per thread in flight before the first one is consumed (clamped addresses, no branches)
-      constexpr int Q4 = KC / 4, PER = 4;
-      const int total = win_rows * Q4;
-      for (int base = tid; base < total; base += RB_THREADS * PER) {
-        float4 v[PER];
-#pragma unroll
-        for (int p = 0; p < PER; ++p) {
-          int e = base + p * RB_THREADS;
-          e = e < total ? e : total - 1;
-          const int wr = e / Q4, c4 = (e % Q4) * 4;
-          const int t = wbase + wr;
-          const int tc = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
-          v[p] = *reinterpret_cast<const float4*>(d.x + (size_t)(tile.seq_begin + tc) * d.ldx + c0 + c4);
-          if (t < 0 || t >= T) v[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int p = 0; p < PER; ++p) {
-          int e = base + p * RB_THREADS;
-          e = e < total ? e : total - 1;
-          const int wr = e / Q4, c4 = (e % Q4) * 4;
-          *reinterpret_cast<uint2*>(xa + wr * XP + c4) =
-              make_uint2(pack16<F16>(v[p].x > 0.f ? v[p].x : v[p].x * d.slope, v[p].y > 0.f ? v[p].y : v[p].y * d.slope),
-                         pack16<F16>(v[p].z > 0.f ? v[p].z : v[p].z * d.slope, v[p].w > 0.f ? v[p].w : v[p].w * d.slope));
         }
       }
     }
@@ -1094,6 +1101,8 @@ int resblock_step(const TtsResblockDesc& d, hipStream_t st) {
   TTS_CHECK_ARG(((uintptr_t)d.b1 & 15) == 0 && ((uintptr_t)d.b2 & 15) == 0, "resblock_step: biases must be 16-byte aligned");
   TTS_CHECK_ARG(!d.io_bf16 || ((d.ldx & 7) == 0 && (d.ldy & 7) == 0 && ((uintptr_t)d.y & 15) == 0), "resblock_step: bf16 rows must be 16-byte aligned");
   TTS_CHECK_ARG(d.compute == 1 || d.compute == 2, "resblock_step: compute must be 1 (bf16) or 2 (fp16), got %d", d.compute);
+  // (the staging addresses x by 32-bit byte offsets from a tile's first fetched row: under 1 024 rows of ldx elements)
+  TTS_CHECK_ARG(d.ldx >= d.c && d.ldx <= (1 << 20), "resblock_step: ldx %d outside [C, 2^20]", d.ldx);
   if (d.n_tiles == 0) return TTS_OK;
 #define TTS_RB(IOB_, F16_)                                                                                  \
   switch (d.c) {                                                                                            \

@@ -133,6 +133,7 @@ int tts_conv1d(const TtsConvDesc* d, tts_stream_t stream);
  * Replaces one dilation step of BigVGAN/AMP.py:53-58 (a1, c1, a2, c2, + x) or Layers/ResidualBlock.py:93-97; with
  * alpha = res_scale = 1/3 and accumulate it also forms the stage mean of InferenceBigVGAN.py:82-88.
  * Weights: bf16 / fp16 [taps][C/8][C][8] as produced for tts_conv1d(compute = 1 / 2).  C in {32, 64, 128, 256}.
+ * C <= ldx <= 2^20 elements (the kernel addresses a tile's window of x by 32-bit offsets).
  */
 typedef struct {
   const float* x; int32_t ldx;
