@@ -249,6 +249,14 @@ PROSODY_PROTOTYPES = {
 }
 PROSODY_SCALES, PROSODY_STATS = 4, 8  # include/toucan_prosody.h TTS_PROSODY_SCALES, TTS_PROSODY_STATS
 
+# symbol -> (restype, argtypes); mirrors include/toucan_prosody_curves.h (per-phoneme prosody curves: csrc/prosody_curves.hip, stage entries in csrc/pipeline.hip)
+CURVE_PROTOTYPES = {
+    "tts_prosody_control_c": (C.c_int, [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "tts_control_and_regulate_c": (C.c_int, [_p, _p, _p, _p, _i, _p, _p]),
+    "tts_copy_prosody_span_stats": (C.c_int, [_p, _p, _p, _p]),
+}
+PROSODY_CURVE_COLUMNS = 5  # include/toucan_prosody_curves.h TTS_PROSODY_CURVE_COLUMNS
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -273,7 +281,7 @@ def lib():
     _assert_single_hip_runtime()
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
-            list(PROSODY_PROTOTYPES.items()):
+            list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

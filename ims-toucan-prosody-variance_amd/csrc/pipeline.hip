@@ -7,6 +7,7 @@
 //   tts_variance_predictors   VariancePredictor.forward / DurationPredictor.inference (VariancePredictor.py:65-80, DurationPredictor.py:63-83)
 //   tts_control_and_regulate  InferenceToucanTTS.py:214-235 (+ _scale_variance :333-343, LengthRegulator.py:37-61)
 //   tts_control_and_regulate_v  the same with per-utterance scales and the statistics around them (include/toucan_prosody.h)
+//   tts_control_and_regulate_c  the same with a per-phoneme curve table and span statistics (include/toucan_prosody_curves.h)
 //   tts_teacher_forced        the scorer's replacement of the two above: ToucanTTS.py:321-330 (include/toucan_score.h)
 //   tts_decoder               decoder Conformer + feat_out (InferenceToucanTTS.py:238-239)
 //   tts_postnet               PostNet.forward + residual (PostNet.py:62-74, InferenceToucanTTS.py:241)
@@ -26,6 +27,7 @@
 
 #include "common.h"
 #include "../../include/toucan_prosody.h"
+#include "../../include/toucan_prosody_curves.h"
 #include "../../include/toucan_score.h"
 
 namespace tts {
@@ -204,6 +206,9 @@ struct Handle {
   std::vector<int> frames;  // per utterance, after the control step
   float* pstats = nullptr;           // [2][B][TTS_PROSODY_STATS] in the phoneme arena: before | after the scales (tts_control_and_regulate_v)
   std::vector<float> pstats_host;    // the same, read back with the durations; empty if the batch went through the scalar entry
+  float* cstats = nullptr;           // [before | after][B][8], then [before | after][n_spans][8], room for B + R rows twice (tts_control_and_regulate_c)
+  int n_spans = -1;                  // spans of the last tts_control_and_regulate_c of the batch in flight; -1: it did not run
+  std::vector<float> sstats_host;    // [2][n_spans][TTS_PROSODY_STATS], read back with the durations
   bool have_flow = false;
   // profiling (bench.py's roofline leg): event pairs around the launches of the selected kernel class ("" = every class)
   bool prof_on = false, prof_detail = false;
@@ -791,7 +796,8 @@ size_t conformer_bytes(size_t R) { return R * (ATT * 4 * 4 + 1536 * 4 + 3 * ATT 
 // Arena sizes: ONE set of expressions for the stage entries (what they reserve) and for tts_workspace_bytes (what it promises).
 size_t phone_arena_bytes(size_t R, size_t B) {
   return conformer_bytes(R) + R * (100 + 3 * ATT + 6 * 256 + 16) * 4 + B * (64 + 2 * ATT + 24 * 256 + 8) * 4 + (1 << 16) +
-         2 * B * TTS_PROSODY_STATS * 4 + 256;  // (the two statistics blocks of tts_control_and_regulate_v)
+         2 * B * TTS_PROSODY_STATS * 4 + 256 +  // (the two statistics blocks of tts_control_and_regulate_v)
+         2 * (B + R) * TTS_PROSODY_STATS * 4 + 256;  // (those of tts_control_and_regulate_c: utterances and at most R spans)
 }
 // cond_buffer: the PostFlow keeps the coupling blocks' conditioning [RS, 1536] in memory (every configuration but the 16-bit ones
 // with the fused WaveNet layer, which computes it inside the layer)
@@ -947,6 +953,9 @@ int pipeline_encoder(Handle* h, const float* text, const float* utt_emb, const i
   h->have_flow = false;
   h->pstats = nullptr;
   h->pstats_host.clear();
+  h->cstats = nullptr;
+  h->n_spans = -1;
+  h->sstats_host.clear();
   const int R = h->lp.total;
   TTS_TRY(arena_reserve(h->phone, phone_arena_bytes(R, B), st));
   TTS_TRY(ensure_ptabs(h, st));
@@ -1123,6 +1132,94 @@ int pipeline_control_regulate_v(Handle* h, const float* scales, int* frames_out,
   TTS_TRY(hip_ok(hipMemcpyAsync(h->pstats_host.data(), h->pstats, 2 * NS * sizeof(float), hipMemcpyDeviceToHost, st), "prosody statistics to host"));
   const int rc = regulate(h, h->dur, false, frames_out, st);  // (synchronises st once: the durations and the statistics are on the host)
   if (rc != TTS_OK) h->pstats_host.clear();
+  return rc;
+}
+
+// ---- stage A.3 / B.0 with a per-phoneme curve table (include/toucan_prosody_curves.h) -------------------------------------------
+// overrides -> statistics (utterances, spans) -> scales and curves -> statistics (utterances, spans), then regulate().  curves: host
+// [R][5], spans: host [n_spans][2] packed row ranges.  Both go up through the table store of the acoustic stages like the scales of
+// the _v entry (pinned staging, one asynchronous copy each on st): the store already orders the reuse of its staging behind the last
+// use of a generation, which a staging buffer beside the phoneme arena would have to do again, and a table that repeats - an emphasis
+// sweep run twice, a server's handful of presets - is found there, not uploaded.  A table that never repeats costs its 20 B per
+// phoneme once in the store and once in the key until the generation passes TABLE_BUDGET and is rewound.
+int pipeline_control_regulate_c(Handle* h, const float* scales, const float* curves, const int* spans, int n_spans, int* frames_out,
+                                hipStream_t st) {
+  TTS_CHECK_ARG(h && h->enc && h->dur, "tts_control_and_regulate_c: run tts_encoder and tts_variance_predictors first");
+  TTS_CHECK_ARG(curves, "tts_control_and_regulate_c: null curves");
+  TTS_CHECK_ARG(n_spans >= 0 && (spans || n_spans == 0), "tts_control_and_regulate_c: %d spans and %s span table", n_spans, spans ? "a" : "no");
+  const int B = h->B, R = h->lp.total;
+  TTS_CHECK_ARG(n_spans <= R, "tts_control_and_regulate_c: %d spans, the entry takes at most one per phoneme row (%d)", n_spans, R);
+  for (int u = 0; u < B; ++u) {
+    if (scales) {
+      const float ds = scales[(size_t)u * TTS_PROSODY_SCALES];
+      TTS_CHECK_ARG(std::isfinite(ds) && ds > 0.f, "tts_control_and_regulate_c: utterance %d: duration_scaling_factor %g must be positive and finite",
+                    u, (double)ds);
+    }
+    for (int i = 0; i < h->lp.lengths[u]; ++i) {
+      const float* c = curves + (size_t)(h->lp.begins[u] + i) * TTS_PROSODY_CURVE_COLUMNS;
+      TTS_CHECK_ARG(std::isfinite(c[0]) && c[0] > 0.f, "tts_control_and_regulate_c: utterance %d, phoneme %d: duration factor %g must be positive and finite",
+                    u, i, (double)c[0]);
+      for (int k = 1; k < TTS_PROSODY_CURVE_COLUMNS; ++k)
+        TTS_CHECK_ARG(std::isfinite(c[k]), "tts_control_and_regulate_c: utterance %d, phoneme %d: curve column %d is %g, it must be finite", u, i, k,
+                      (double)c[k]);
+    }
+  }
+  for (int s = 0; s < n_spans; ++s)
+    TTS_CHECK_ARG(0 <= spans[2 * s] && spans[2 * s] <= spans[2 * s + 1] && spans[2 * s + 1] <= R,
+                  "tts_control_and_regulate_c: span %d is rows [%d, %d), the batch has %d", s, spans[2 * s], spans[2 * s + 1], R);
+  TTS_CHECK_RESOLVED(h, "tts_control_and_regulate_c");
+  h->tab_which = 0;
+  const int *pb, *pe;
+  TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
+  // (keys: a layout key is 4 (2 n + 1) bytes of begins and lengths; these start with a name, as the _v entry's does)
+  void *sdev = nullptr, *cdev = nullptr, *bdev = nullptr;
+  if (scales) {
+    std::string key("prosody_scales");
+    key.append(reinterpret_cast<const char*>(scales), (size_t)B * TTS_PROSODY_SCALES * sizeof(float));
+    TTS_TRY(table_of(h, key, st, [&] { return std::vector<float>(scales, scales + (size_t)B * TTS_PROSODY_SCALES); }, &sdev, nullptr));
+  }
+  {
+    std::string key("prosody_curves");
+    key.append(reinterpret_cast<const char*>(curves), (size_t)R * TTS_PROSODY_CURVE_COLUMNS * sizeof(float));
+    TTS_TRY(table_of(h, key, st, [&] { return std::vector<float>(curves, curves + (size_t)R * TTS_PROSODY_CURVE_COLUMNS); }, &cdev, nullptr));
+  }
+  if (n_spans > 0) {  // (begin[n_spans] | end[n_spans]), the form tts_prosody_stats takes
+    std::string key("prosody_spans");
+    key.append(reinterpret_cast<const char*>(spans), (size_t)n_spans * 2 * sizeof(int));
+    TTS_TRY(table_of(h, key, st, [&] {
+      std::vector<int> host(2 * (size_t)n_spans);
+      for (int s = 0; s < n_spans; ++s) {
+        host[s] = spans[2 * s];
+        host[n_spans + s] = spans[2 * s + 1];
+      }
+      return host;
+    }, &bdev, nullptr));
+  }
+  const int *xb = static_cast<const int*>(bdev), *xe = xb ? xb + n_spans : nullptr;
+  const size_t NU = (size_t)B * TTS_PROSODY_STATS, NX = (size_t)n_spans * TTS_PROSODY_STATS;
+  if (!h->cstats) {
+    TTS_ALLOC(cs, h->phone, float, 2 * (size_t)(B + R) * TTS_PROSODY_STATS);
+    h->cstats = cs;
+  }
+  float *ubefore = h->cstats, *uafter = ubefore + NU, *xbefore = uafter + NU, *xafter = xbefore + NX;
+  TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, nullptr, st));
+  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, ubefore, st));
+  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, xb, xe, n_spans, xbefore, st));
+  TTS_TRY(tts_prosody_control_c(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, static_cast<const float*>(sdev),
+                                static_cast<const float*>(cdev), st));
+  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, uafter, st));
+  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, xb, xe, n_spans, xafter, st));
+  h->pstats_host.assign(2 * NU, 0.f);
+  h->sstats_host.assign(2 * NX, 0.f);
+  TTS_TRY(hip_ok(hipMemcpyAsync(h->pstats_host.data(), ubefore, 2 * NU * sizeof(float), hipMemcpyDeviceToHost, st), "prosody statistics to host"));
+  if (n_spans > 0)
+    TTS_TRY(hip_ok(hipMemcpyAsync(h->sstats_host.data(), xbefore, 2 * NX * sizeof(float), hipMemcpyDeviceToHost, st), "span statistics to host"));
+  const int rc = regulate(h, h->dur, false, frames_out, st);  // (synchronises st once: durations and statistics are on the host)
+  h->n_spans = rc == TTS_OK ? n_spans : -1;
+  if (rc != TTS_OK) {
+    h->pstats_host.clear();
+    h->sstats_host.clear();
+  }
   return rc;
 }
 
@@ -1579,6 +1676,22 @@ int tts_copy_prosody_stats(TtsHandle* h, float* before, float* after, tts_stream
   const size_t n = (size_t)hh->B * TTS_PROSODY_STATS;
   if (before) memcpy(before, hh->pstats_host.data(), n * sizeof(float));
   if (after) memcpy(after, hh->pstats_host.data() + n, n * sizeof(float));
+  return TTS_OK;
+}
+int tts_control_and_regulate_c(TtsHandle* h, const float* scales, const float* curves, const int32_t* spans, int32_t n_spans,
+                               int32_t* frame_counts, tts_stream_t stream) {
+  return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_control_regulate_c(H(h), scales, curves, spans, n_spans, frame_counts, ST(stream)));
+}
+int tts_copy_prosody_span_stats(TtsHandle* h, float* before, float* after, tts_stream_t stream) {
+  (void)stream;  // (the blocks came back with the durations: a host copy)
+  tts::Handle* hh = H(h);
+  if (!hh || hh->n_spans < 0) {
+    tts::set_error("tts_copy_prosody_span_stats: the batch in flight did not go through tts_control_and_regulate_c");
+    return TTS_E_ARG;
+  }
+  const size_t n = (size_t)hh->n_spans * TTS_PROSODY_STATS;
+  if (before && n) memcpy(before, hh->sstats_host.data(), n * sizeof(float));
+  if (after && n) memcpy(after, hh->sstats_host.data() + n, n * sizeof(float));
   return TTS_OK;
 }
 int tts_teacher_forced(TtsHandle* h, const float* gold_pitch, const float* gold_energy, const int32_t* gold_durations, float* pred_log_dur,

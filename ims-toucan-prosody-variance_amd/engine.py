@@ -310,6 +310,23 @@ class Ops:
                                               stats.data_ptr(), self.stream()), "tts_prosody_stats")
         return stats
 
+    def prosody_control_c(self, text, pitch, energy, dur, rag, scales, curves):
+        """tts_prosody_control_v with every scale multiplied row by row by ``curves`` ([rows, 5] float32 on the device) and the two
+        offsets behind the variance scales (include/toucan_prosody_curves.h); scales None: all 1."""
+        sb, se = rag.bounds()
+        assert curves.dtype == torch.float32 and curves.is_contiguous() and tuple(curves.shape) == (rag.total_rows, capi.PROSODY_CURVE_COLUMNS)
+        capi.check(self.lib.tts_prosody_control_c(text.data_ptr(), _ld(text), pitch.data_ptr(), energy.data_ptr(), dur.data_ptr(),
+                                                  sb.data_ptr(), se.data_ptr(), rag.n_seq, _ptr(scales), curves.data_ptr(), self.stream()),
+                   "tts_prosody_control_c")
+
+    def prosody_span_stats(self, pitch, energy, dur, ranges, stats):
+        """tts_prosody_stats over arbitrary packed row ranges: ``ranges`` = (begin[n] | end[n]) as an int32 [2, n] device tensor."""
+        n = int(ranges.shape[1])
+        assert ranges.dtype == torch.int32 and ranges.is_contiguous() and ranges.shape[0] == 2 and tuple(stats.shape) == (n, capi.PROSODY_STATS)
+        capi.check(self.lib.tts_prosody_stats(pitch.data_ptr(), energy.data_ptr(), dur.data_ptr(), ranges[0].data_ptr(), ranges[1].data_ptr(), n,
+                                              stats.data_ptr(), self.stream()), "tts_prosody_stats")
+        return stats
+
     def length_regulate(self, enc, pitch, energy, wp, bp, we, be, dur, rag_phone, rag_frame, up, dec_in, dec_scale):
         pb, pe = rag_phone.bounds()
         fb, _ = rag_frame.bounds()
@@ -607,8 +624,10 @@ class AcousticEngine:
         return out.view(-1)
 
     # ---- stage A: everything up to the final per-phoneme durations (no data-dependent shapes) ----------------
-    def _stage_a(self, text, emb, lang_idx, gold_p, gold_e, gold_d, rag_p, rag_b, scales, taps=None):
-        """Conformer.py:92-134, VariancePredictor / DurationPredictor, InferenceToucanTTS.py:214-227."""
+    def _stage_a(self, text, emb, lang_idx, gold_p, gold_e, gold_d, rag_p, rag_b, scales, taps=None, curves=None, ranges=None):
+        """Conformer.py:92-134, VariancePredictor / DurationPredictor, InferenceToucanTTS.py:214-227.  curves ([R, 5] device table,
+        then ``scales`` is a [B, 4] tensor or None) and ranges ((begin | end) [2, n] of the spans, or None): the launches of
+        tts_control_and_regulate_c in its order."""
         ops = self.ops
         ops.split_k = 2  # phoneme stages (fp32 configuration): the split forms at every grid size - see Ops.__init__
         R, B = text.shape[0], emb.shape[0]
@@ -650,6 +669,18 @@ class AcousticEngine:
             d.copy_(gold_d)
         if taps is not None:
             taps.update(enc_out=enc.clone(), pitch_raw=p.clone(), energy_raw=en.clone())
+        if curves is not None:  # per-phoneme curves: overrides -> statistics (utterances, spans) -> scales and curves -> statistics
+            n = 0 if ranges is None else int(ranges.shape[1])
+            stats, span_stats = ops.empty(2, B, capi.PROSODY_STATS), ops.empty(2, max(n, 1), capi.PROSODY_STATS)
+            ops.prosody_control_v(text, p, en, d, rag_p, None)
+            ops.prosody_stats(p, en, d, rag_p, stats[0])
+            if n:
+                ops.prosody_span_stats(p, en, d, ranges, span_stats[0])
+            ops.prosody_control_c(text, p, en, d, rag_p, scales, curves)
+            ops.prosody_stats(p, en, d, rag_p, stats[1])
+            if n:
+                ops.prosody_span_stats(p, en, d, ranges, span_stats[1])
+            return enc, p, en, d, stats, span_stats[:, :n]
         if torch.is_tensor(scales):  # per-utterance scales [B, 4]: overrides -> statistics -> scales -> statistics
             stats = ops.empty(2, B, capi.PROSODY_STATS)
             ops.prosody_control_v(text, p, en, d, rag_p, None)
@@ -692,11 +723,17 @@ class AcousticEngine:
     @torch.inference_mode()
     def forward(self, texts, utt_embs, lang_ids=None, durations=None, pitch=None, energy=None, z_noise=None,
                 duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
-                pause_duration_scaling_factor=1.0, run_postflow=True, taps=None, generator=None):
+                pause_duration_scaling_factor=1.0, run_postflow=True, taps=None, generator=None, prosody_curves=None):
         """texts: list of [L_u,62] float tensors; utt_embs: [B,64]; lang_ids: list of int or None;
         durations/pitch/energy: optional lists (gold values, InferenceToucanTTS.py:209-211);
         the four scales: a scalar for the batch, or one value per utterance (any sequence takes the per-utterance kernels and adds
         ``prosody_stats`` = (before, after), float32 [B, 8] arrays with the columns prosody.STATS, to the result);
+        prosody_curves: None, or per utterance None / an [L_u, 5] array (columns prosody.CURVE_COLUMNS) / a list of prosody.Span
+        (prosody.resolve_curves).  With curves the result has ``prosody_stats`` as above and
+        ``prosody_span_stats``: per utterance (before [n, 8], after [n, 8]) for its Spans in list order, empty for array curves.
+        Column 6 of a Span's block is the frames the Span occupies after the curves; with the frames of the phonemes in front of it
+        (``durations``) that tells which samples carry the emphasised word.  A zero entry inside a Span scaled below 1 becomes
+        mean * (1 - scale), as the reference's _scale_variance does for a whole call;
         z_noise: optional list of [80, T_u] tensors = 0.8*N(0,1) (Glow.py:363) - drawn on the device if omitted.
         Returns dict(mel=[list of [T'_u,80]], durations, pitch, energy, plus packed tensors).
 
@@ -706,12 +743,17 @@ class AcousticEngine:
         if self.device.type == "cuda" and torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):  # launches go to streams of self.device: it must be the current HIP device
                 return self.forward(texts, utt_embs, lang_ids, durations, pitch, energy, z_noise, duration_scaling_factor,
-                                    pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor, run_postflow, taps, generator)
+                                    pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor, run_postflow, taps, generator,
+                                    prosody_curves)
         ops, dev = self.ops, self.device
         B = len(texts)
-        table = prosody.resolve_scales(B, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor)
-        assert table is not None or duration_scaling_factor > 0
         Ls = [int(t.shape[0]) for t in texts]
+        curves = prosody.resolve_curves(Ls, prosody_curves)
+        if curves is not None:
+            table = prosody.broadcast_scales(B, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor)
+        else:
+            table = prosody.resolve_scales(B, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor)
+        assert table is not None or duration_scaling_factor > 0
         rag_p = Ragged.cached(Ls, dev)
         rag_b = Ragged.cached([B], dev)
         text = torch.cat([t.reshape(-1, 62).to(torch.float32) for t in texts], dim=0).to(dev).contiguous()
@@ -725,8 +767,19 @@ class AcousticEngine:
             lang_idx = torch.tensor([int(i) for i in lang_ids], dtype=torch.int32).to(dev)
         gp, ge, gd = packed_gold(pitch, torch.float32), packed_gold(energy, torch.float32), packed_gold(durations, torch.int32)
         graphs = self.use_graphs and taps is None and dev.type == "cuda"
-        stats = None
-        if table is not None:  # per-utterance scales: a device table, an input of the captured graph like the text
+        stats = span_stats = None
+        if curves is not None:  # per-phoneme curves: the table, the scales and the span ranges are inputs of the captured graph
+            ctab, ranges, span_counts = curves
+            n = int(ranges.shape[0])
+            ins = dict(scales=None if table is None else torch.from_numpy(table).to(dev), curves=torch.from_numpy(ctab).to(dev),
+                       ranges=torch.from_numpy(np.ascontiguousarray(ranges.T)).to(dev) if n else None)
+            if graphs:  # (one graph per shape: the values of all three are copied into its buffers before the replay)
+                key = ("A", tuple(Ls), lang_idx is not None, gp is not None, ge is not None, gd is not None, "curves", table is not None, n)
+                ins.update(text=text, emb=emb, lang_idx=lang_idx, gold_p=gp, gold_e=ge, gold_d=gd)
+                enc, p, en, d, stats, span_stats = self._graphs.run(key, ins, lambda **kw: self._stage_a(rag_p=rag_p, rag_b=rag_b, **kw))
+            else:
+                enc, p, en, d, stats, span_stats = self._stage_a(text, emb, lang_idx, gp, ge, gd, rag_p, rag_b, taps=taps, **ins)
+        elif table is not None:  # per-utterance scales: a device table, an input of the captured graph like the text
             scales = torch.from_numpy(table).to(dev)
             if graphs:
                 key = ("A", tuple(Ls), lang_idx is not None, gp is not None, ge is not None, gd is not None, "per-utterance scales")
@@ -780,6 +833,9 @@ class AcousticEngine:
         if stats is not None:
             stats = stats.cpu().numpy()
             out["prosody_stats"] = (stats[0], stats[1])
+        if span_stats is not None:
+            span_stats = span_stats.cpu().numpy()
+            out["prosody_span_stats"] = prosody.split_span_stats((span_stats[0], span_stats[1]), span_counts)
         return out
 
     @torch.inference_mode()

@@ -11,7 +11,7 @@ script written against the reference (run_text_to_file_reader.py:8-16) works unc
   strings skipped, 24 kHz output or sample-doubled 48 kHz PCM16), ``read_aloud`` (:287-309), the language / embedding setters
 * additive API: ``synthesize_batch`` (ragged batches, optionally sharded over the ranks of torch.distributed; every prosody scale
   a scalar or one value per utterance), ``synthesize_grid`` (one text over a grid of prosody scales, with the statistics of what
-  each scale did)
+  each scale did), ``prosody_curves=`` / ``curves=`` (per-phoneme prosody curves: stress one word, prosody.emphasis)
 
 * ``set_utterance_embedding(path)`` (:103-114): reference audio -> log-mel -> GST style embedding on the GPU (style.py)
 
@@ -158,7 +158,8 @@ class ToucanTTSInterface(torch.nn.Module):
 
         self.embedding_model_path = embedding_model_path  # GST network: loaded on the first set_utterance_embedding(path)
         self._style = None
-        self.last_prosody_stats = None  # (before, after) of the last batch that took per-utterance prosody scales
+        self.last_prosody_stats = None  # (before, after) of the last batch that took per-utterance prosody scales or curves
+        self.last_prosody_span_stats = None  # per utterance (before, after) of its Spans, of the last batch that took prosody curves
 
 
         self.default_utterance_embedding = checkpoint["default_emb"].to(self.device)
@@ -210,14 +211,18 @@ class ToucanTTSInterface(torch.nn.Module):
                 return_plot_as_filepath=False,
                 z_noise=None,
                 sample_rate=None,
-                pcm16=False):
+                pcm16=False,
+                prosody_curves=None):
         """The reference's signature (ToucanTTSInterface.py:132-143) plus additive keywords.  ``z_noise`` [80, T]: the PostFlow
         noise 0.8 N(0,1) the reference draws inside the model (Glow.py:363), so that a call can be reproduced and checked
         against the oracle; None draws it on the device.  ``sample_rate`` / ``pcm16``: the waveform at another rate than 24 kHz
-        and / or as int16, converted on the device (resample.py); the figure of ``view`` keeps drawing the 24 kHz wave."""
+        and / or as int16, converted on the device (resample.py); the figure of ``view`` keeps drawing the 24 kHz wave.
+        ``prosody_curves``: this utterance's per-phoneme curves, an [L, 5] array or a list of ``prosody.Span`` (as one entry of
+        ``synthesize_batch``'s keyword, documented there); None is the call as it was."""
         self._check_output_format(sample_rate, pcm16)
         with torch.inference_mode():
             phones = self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
+            curves = {} if prosody_curves is None else dict(prosody_curves=[prosody_curves])
             wav24, spans = self._synthesize_packed([phones], [self.default_utterance_embedding], [self._lang()],
                                                    z_noise=None if z_noise is None else [z_noise],
                                                    durations=None if durations is None else [durations],
@@ -225,7 +230,7 @@ class ToucanTTSInterface(torch.nn.Module):
                                                    energy=None if energy is None else [energy],
                                                    duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
                                                    energy_variance_scale=energy_variance_scale,
-                                                   pause_duration_scaling_factor=pause_duration_scaling_factor)
+                                                   pause_duration_scaling_factor=pause_duration_scaling_factor, **curves)
             wav, out_spans = self._convert(wav24, spans, sample_rate, pcm16)
             wavs = [wav[b:b + n] for b, n in out_spans]
         if view or return_plot_as_filepath:  # ToucanTTSInterface.py:171-226 (matplotlib only: plotting.py)
@@ -251,12 +256,14 @@ class ToucanTTSInterface(torch.nn.Module):
             self.last_durations, self.last_pitch, self.last_energy = out["durations"], out["pitch"], out["energy"]
             self.last_mel = out["mel"]
             self.last_prosody_stats = out.get("prosody_stats")
+            self.last_prosody_span_stats = out.get("prosody_span_stats")
             return out["wav"], out["wav_spans"]
         out = self.phone2mel.forward(phones, emb, lang_ids, z_noise=z_noise, **kw)
         wav, rag = self.mel2wav.forward(out["mel_packed"], out["rag_mel"])
         self.last_durations, self.last_pitch, self.last_energy = out["durations"], out["pitch"], out["energy"]
         self.last_mel = out["mel"]
         self.last_prosody_stats = out.get("prosody_stats")
+        self.last_prosody_span_stats = out.get("prosody_span_stats")
         return wav, list(zip(rag.begins, rag.lengths))
 
     def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, **kw):
@@ -296,7 +303,7 @@ class ToucanTTSInterface(torch.nn.Module):
 
     def synthesize_batch(self, texts, input_is_phones=True, utterance_embeddings=None, z_noise=None, durations=None, pitch=None,
                          energy=None, duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
-                         pause_duration_scaling_factor=1.0, distributed=False, sample_rate=None, pcm16=False):
+                         pause_duration_scaling_factor=1.0, distributed=False, sample_rate=None, pcm16=False, prosody_curves=None):
         """Additive API: a ragged batch in one pass; each utterance equals the reference run on it alone (16-bit configurations: bit
         for bit whatever the batch; fp32: durations / pitch / energy bit for bit, the mel to fp32 rounding order - DESIGN.md section 4).
         texts: phoneme strings (or [L,62] feature tensors).  durations / pitch / energy: optional per-utterance gold prosody (the
@@ -308,7 +315,20 @@ class ToucanTTSInterface(torch.nn.Module):
         ``self.last_prosody_stats`` = (before, after): float32 [B, 8] arrays (columns ``prosody.STATS``) of every utterance's pitch /
         energy / durations before and after its scales; an all-scalar call leaves None there.  ValueError for a sequence of the
         wrong length, a duration factor that is not positive (the message names the utterance), and sequences with
-        ``distributed=True`` (the sharded deal does not carry them)."""
+        ``distributed=True`` (the sharded deal does not carry them).
+        ``prosody_curves``: None, or a list with one entry per utterance - None, a float [L_u, 5] array with the columns
+        ``prosody.CURVE_COLUMNS`` (duration factor, pitch variance scale, energy variance scale, all neutral at 1; pitch offset, energy
+        offset, neutral at 0) or a list of ``prosody.Span`` (``prosody.emphasis(feats, [k])`` stresses word k), overlapping Spans
+        multiplying their factors and adding their offsets.  Every phoneme's effective scale is the utterance's scale times its
+        curve value: a variance scale moves the phoneme away from (above 1) or towards (below 1) the mean of
+        the WHOLE utterance's non-zero entries, an offset is added to non-zero entries afterwards, both clamp at 0, and a phoneme
+        whose five values are neutral keeps the bits of the call without curves.  The reference's quirk is kept: a zero entry (an
+        unvoiced phoneme, a pause) inside a Span scaled below 1 becomes mean * (1 - scale).  A call with curves leaves
+        ``self.last_prosody_stats`` as above and ``self.last_prosody_span_stats``: per utterance (before [n, 8], after [n, 8]) for its
+        Spans in list order (empty for arrays); column 6 of a Span's block is the frames it occupies after the curves, which with the
+        frames in front of it (``self.last_durations``) tells which samples carry the emphasised word.  ValueError for a wrong
+        shape, a Span outside its utterance, a value that is not finite or a duration factor that is not positive (the message
+        names the utterance and the phoneme), and for curves with ``distributed=True``."""
         if distributed and (sample_rate is not None or pcm16):
             raise ValueError("sample_rate / pcm16 are not available with distributed=True: the sharded exchange carries 24 kHz float32")
         self._check_output_format(sample_rate, pcm16)
@@ -316,11 +336,16 @@ class ToucanTTSInterface(torch.nn.Module):
                                                pause_duration_scaling_factor) is not None
         if distributed and per_utterance:
             raise ValueError("per-utterance prosody scales are not available with distributed=True: the sharded deal carries scalars")
+        if distributed and prosody_curves is not None:
+            raise ValueError("prosody curves are not available with distributed=True: the sharded deal carries scalars")
         feats = [t if torch.is_tensor(t) else self.text2phone.string_to_tensor(t, input_phonemes=input_is_phones) for t in texts]
         embs = utterance_embeddings if utterance_embeddings is not None else [self.default_utterance_embedding] * len(feats)
         kw = dict(duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
                   energy_variance_scale=energy_variance_scale, pause_duration_scaling_factor=pause_duration_scaling_factor)
         if not distributed:
+            if prosody_curves is not None:
+                prosody.resolve_curves([int(f.shape[0]) for f in feats], prosody_curves)  # (ValueError before anything runs)
+                kw["prosody_curves"] = prosody_curves
             with torch.inference_mode():
                 return self._synthesize(feats, embs, [self._lang()] * len(feats), z_noise=z_noise, durations=durations, pitch=pitch,
                                         energy=energy, sample_rate=sample_rate, pcm16=pcm16, **kw)
@@ -346,7 +371,7 @@ class ToucanTTSInterface(torch.nn.Module):
 
     def synthesize_grid(self, text, duration_scaling_factors=(1.0,), pitch_variance_scales=(1.0,), energy_variance_scales=(1.0,),
                         pause_duration_scaling_factors=(1.0,), input_is_phones=True, utterance_embedding=None, durations=None, pitch=None,
-                        energy=None, z_noise=None, sample_rate=None, pcm16=False):
+                        energy=None, z_noise=None, sample_rate=None, pcm16=False, curves=None):
         """Additive API: ONE text (a phoneme string, or its [L, 62] feature tensor) at every combination of the four tuples of prosody scales - the Cartesian product in row-major
         order of the tuples as listed (the pause factor varies fastest) - synthesised as ragged batches of at most MAX_FILE_BATCH
         variants with per-utterance scales instead of one pass per setting.  Returns one dict per variant, in that order:
@@ -355,9 +380,21 @@ class ToucanTTSInterface(torch.nn.Module):
         overrides, before and after its scales - their ratio is what a scale really did, the reference's clamp at 0 and its shift of
         the zeros included).  Every variant equals ``forward`` of the text with its four scalars.  durations / pitch / energy: gold
         prosody of the text, shared by the variants; ``z_noise``: None or one [80, T] entry per variant; ``sample_rate`` / ``pcm16`` as
-        in ``forward``.  The variants are replicated on the host: every one runs the whole model."""
+        in ``forward``.  The variants are replicated on the host: every one runs the whole model.
+        ``curves``: None, or a list of K alternative per-phoneme curves of the text (each None, an [L, 5] array or a list of
+        ``prosody.Span``, as one entry of ``synthesize_batch``'s ``prosody_curves``).  They form a fifth, SLOWEST axis of the product:
+        all scale variants under curves[0], then under curves[1], ...  The dicts then also hold ``curve`` (the index into
+        ``curves``) and ``span_stats`` = (before [n, 8], after [n, 8]) of that alternative's Spans; column 6 of a Span's block is the
+        frames it occupies.  ``curves=[prosody.emphasis(feats, [k]) for k in range(len(prosody.word_spans(feats)))]`` is the emphasis
+        sweep over the words of a sentence in one call."""
         self._check_output_format(sample_rate, pcm16)
         variants = prosody.grid(duration_scaling_factors, pitch_variance_scales, energy_variance_scales, pause_duration_scaling_factors)
+        which = [None] * len(variants)  # the curve alternative of every variant
+        if curves is not None:
+            if len(curves) == 0:
+                raise ValueError("every axis of a prosody grid needs at least one value")
+            which = [k for k in range(len(curves)) for _ in variants]
+            variants = variants * len(curves)
         if z_noise is not None and len(z_noise) != len(variants):
             raise ValueError(f"z_noise holds {len(z_noise)} entries, the grid has {len(variants)} variants")
         prosody.resolve_scales(len(variants), *[[v[k] for v in variants] for k in range(4)])  # (the duration factors, before anything runs)
@@ -365,31 +402,38 @@ class ToucanTTSInterface(torch.nn.Module):
         results = []
         with torch.inference_mode():
             phones = text if torch.is_tensor(text) else self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
+            if curves is not None:
+                prosody.resolve_curves([int(phones.shape[0])] * len(curves), curves)  # (ValueError before anything runs; "utterance" = alternative)
             for lo in range(0, len(variants), self.MAX_FILE_BATCH):
                 chunk = variants[lo:lo + self.MAX_FILE_BATCH]
                 n = len(chunk)
                 rep = lambda v: None if v is None else [v] * n
+                kw = {} if curves is None else dict(prosody_curves=[curves[k] for k in which[lo:lo + n]])
                 wav24, spans24 = self._synthesize_packed([phones] * n, [emb] * n, [self._lang()] * n,
                                                          z_noise=None if z_noise is None else list(z_noise[lo:lo + n]),
                                                          durations=rep(durations), pitch=rep(pitch), energy=rep(energy),
-                                                         **{name: [v[k] for v in chunk] for k, name in enumerate(prosody.KNOBS)})
+                                                         **{name: [v[k] for v in chunk] for k, name in enumerate(prosody.KNOBS)}, **kw)
                 before, after = self.last_prosody_stats
                 wav, spans = self._convert(wav24, spans24, sample_rate, pcm16)
                 for i, scales in enumerate(chunk):
                     results.append({"scales": scales, "wave": wav[spans[i][0]:spans[i][0] + spans[i][1]], "frames": int(spans24[i][1]) // 384,
                                     "stats_before": before[i], "stats_after": after[i]})
+                    if curves is not None:  # (a chunk whose alternatives are all None took the path without curves: no Spans, no blocks)
+                        none = np.zeros((0, len(prosody.STATS)), dtype=np.float32)
+                        per = self.last_prosody_span_stats
+                        results[-1].update(curve=which[lo + i], span_stats=(none, none) if per is None else per[i])
         return results
 
     def stream(self, text, input_is_phones=False, chunk_frames=512, halo_frames=None, max_batch=4, z_noise=None, sample_rate=None, pcm16=False, **prosody):
         """Generator of waveform pieces for ONE (long) text: the acoustic model runs once, the vocoder chunk-wise with overlap
         (streaming.py) - the concatenation equals ``self(text, ...)`` bit for bit, the first piece is ready after one chunk and the
         vocoder's workspace is bounded by ``max_batch`` chunks.  prosody: the keyword arguments of ``forward`` (gold durations /
-        pitch / energy, scaling factors).  ``sample_rate`` / ``pcm16``: the pieces at another rate and / or as int16, converted as
+        pitch / energy, scaling factors, ``prosody_curves``).  ``sample_rate`` / ``pcm16``: the pieces at another rate and / or as int16, converted as
         they come (resample.Resampler.streamer); their concatenation equals ``self(text, sample_rate=..., pcm16=...)`` bit for bit."""
         from . import streaming
         convert = self._check_output_format(sample_rate, pcm16)
         halo = streaming.DEFAULT_HALO if halo_frames is None else halo_frames
-        listed = {k: [v] for k, v in prosody.items() if k in ("durations", "pitch", "energy") and v is not None}
+        listed = {k: [v] for k, v in prosody.items() if k in ("durations", "pitch", "energy", "prosody_curves") and v is not None}
         scales = {k: v for k, v in prosody.items() if k.endswith("_factor") or k.endswith("_scale")}
         with torch.inference_mode():
             phones = self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
@@ -402,6 +446,8 @@ class ToucanTTSInterface(torch.nn.Module):
                 out = self.phone2mel.forward([phones], emb, langs, z_noise=None if z_noise is None else [z_noise], **listed, **scales)
                 vocode = self.mel2wav.forward
             self.last_durations, self.last_pitch, self.last_energy = out["durations"], out["pitch"], out["energy"]
+            if "prosody_curves" in listed:
+                self.last_prosody_stats, self.last_prosody_span_stats = out.get("prosody_stats"), out.get("prosody_span_stats")
             pieces = streaming.stream_vocode(vocode, out["mel"][0].contiguous(), chunk_frames, halo, max_batch)
             if not convert:
                 yield from pieces

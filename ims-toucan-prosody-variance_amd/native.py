@@ -49,7 +49,8 @@ class NativePipeline:
         voc = None
         self.kind = vocoder_kind
         self._streams = None  # (acoustic, vocoder) stream pair of forward_pipelined, made on first use
-        self._prosody_stats = None  # (before, after) of the last stage A that took per-utterance scales
+        self._prosody_stats = None  # (before, after) of the last stage A that took per-utterance scales or curves
+        self._prosody_span_stats = None  # per utterance (before, after) of its Spans, of the last stage A that took curves
         if vocoder_sd is not None:
             assert vocoder_kind in ("hifigan", "bigvgan")
             voc = engine.VocoderEngine(vocoder_sd, vocoder_kind, "cpu", precision=self.vocoder_precision, pack_only=True)
@@ -281,17 +282,35 @@ class NativePipeline:
             z_sq[b0:b0 + n].copy_(torch.as_tensor(zu, dtype=torch.float32).t()[: 2 * n].reshape(n, 160))
         return z_sq
 
-    def _stage_a(self, packed, duration_scale, pitch_scale, energy_scale, pause_scale, st):
+    def _stage_a(self, packed, duration_scale, pitch_scale, energy_scale, pause_scale, st, prosody_curves=None):
         """Stage A on a packed batch (tts_encoder, tts_variance_predictors, tts_control_and_regulate - or its _v form when a scale is a
-        sequence: one value per utterance, scalars among them broadcast): mel frames per utterance."""
+        sequence: one value per utterance, scalars among them broadcast - or its _c form with per-phoneme curves): mel frames per
+        utterance."""
         lib, Ls = self.lib, packed["Ls"]
         B = len(Ls)
-        table = prosody.resolve_scales(B, duration_scale, pitch_scale, energy_scale, pause_scale)  # (ValueError before anything is enqueued)
+        curves = prosody.resolve_curves(Ls, prosody_curves)  # (ValueError before anything is enqueued)
+        if curves is not None:
+            table = prosody.broadcast_scales(B, duration_scale, pitch_scale, energy_scale, pause_scale)
+        else:
+            table = prosody.resolve_scales(B, duration_scale, pitch_scale, energy_scale, pause_scale)
         self._ensure_pe(max(Ls))
         capi.check(lib.tts_encoder(self.h, ptr(packed["text"]), ptr(packed["emb"]), ptr(packed["lang"]), (C.c_int32 * B)(*Ls), B, st), "tts_encoder")
         capi.check(lib.tts_variance_predictors(self.h, ptr(packed["gp"]), ptr(packed["ge"]), ptr(packed["gd"]), st), "tts_variance_predictors")
         frames = (C.c_int32 * B)()
-        self._prosody_stats = None
+        self._prosody_stats = self._prosody_span_stats = None
+        fptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        if curves is not None:  # per-phoneme curves (include/toucan_prosody_curves.h): both kinds of statistics come back with the durations
+            ctab, ranges, counts = curves
+            n = int(ranges.shape[0])
+            capi.check(lib.tts_control_and_regulate_c(self.h, None if table is None else fptr(table), fptr(ctab), fptr(ranges) if n else None, n,
+                                                      frames, st), "tts_control_and_regulate_c")
+            before, after = (np.empty((B, capi.PROSODY_STATS), dtype=np.float32) for _ in range(2))
+            capi.check(lib.tts_copy_prosody_stats(self.h, fptr(before), fptr(after), st), "tts_copy_prosody_stats")
+            sb, sa = (np.empty((n, capi.PROSODY_STATS), dtype=np.float32) for _ in range(2))
+            capi.check(lib.tts_copy_prosody_span_stats(self.h, fptr(sb), fptr(sa), st), "tts_copy_prosody_span_stats")
+            self._prosody_stats = (before, after)
+            self._prosody_span_stats = prosody.split_span_stats((sb, sa), counts)
+            return [int(f) for f in frames]
         if table is None:
             capi.check(lib.tts_control_and_regulate(self.h, float(duration_scale), float(pitch_scale), float(energy_scale), float(pause_scale), frames, st),
                        "tts_control_and_regulate")
@@ -306,23 +325,27 @@ class NativePipeline:
     @torch.inference_mode()
     def forward(self, texts, utt_embs, lang_ids=None, durations=None, pitch=None, energy=None, z_noise=None, duration_scaling_factor=1.0,
                 pitch_variance_scale=1.0, energy_variance_scale=1.0, pause_duration_scaling_factor=1.0, run_postflow=True, vocode=True,
-                generator=None, packed=None, z_sq=None):
+                generator=None, packed=None, z_sq=None, prosody_curves=None):
         """Same arguments and result keys as engine.AcousticEngine.forward (+ ``wav`` / ``wav_spans`` when a vocoder is loaded and
-        ``vocode``; ``prosody_stats`` when a scale is a sequence).  Every stage is one call into libtoucan_hip.so."""
+        ``vocode``; ``prosody_stats`` when a scale is a sequence; ``prosody_stats`` and ``prosody_span_stats`` with ``prosody_curves``,
+        documented there).  Every stage is one call into libtoucan_hip.so."""
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
                 return self.forward(texts, utt_embs, lang_ids, durations, pitch, energy, z_noise, duration_scaling_factor, pitch_variance_scale,
-                                    energy_variance_scale, pause_duration_scaling_factor, run_postflow, vocode, generator, packed, z_sq)
+                                    energy_variance_scale, pause_duration_scaling_factor, run_postflow, vocode, generator, packed, z_sq,
+                                    prosody_curves)
         dev, lib, st = self.device, self.lib, self._stream()
         assert np.ndim(duration_scaling_factor) > 0 or duration_scaling_factor > 0  # (a sequence is checked per utterance in _stage_a)
         if packed is None:
             packed = self.pack_inputs(texts, utt_embs, lang_ids, durations, pitch, energy)
         Ls = packed["Ls"]
-        Ts = self._stage_a(packed, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor, st)
+        Ts = self._stage_a(packed, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor, st,
+                           prosody_curves)
         if max(Ts) > self._pmax:  # longer than the position table: enlarge it and redo the (cheap) phoneme stages
             self._ensure_pe(max(Ts))
             return self.forward(texts, utt_embs, lang_ids, durations, pitch, energy, z_noise, duration_scaling_factor, pitch_variance_scale,
-                                energy_variance_scale, pause_duration_scaling_factor, run_postflow, vocode, generator, packed, z_sq)
+                                energy_variance_scale, pause_duration_scaling_factor, run_postflow, vocode, generator, packed, z_sq,
+                                prosody_curves)
         rag_p = Ragged(Ls, dev)
         rag_f = Ragged(Ts, dev, align=2)
         capi.check(lib.tts_decoder(self.h, st), "tts_decoder")
@@ -350,6 +373,8 @@ class NativePipeline:
         out = dict(durations_packed=d, pitch_packed=p, energy_packed=en, rag_phone=rag_p, rag_frame=rag_f, mel_packed=mel_packed, rag_mel=rag_out)
         if self._prosody_stats is not None:
             out["prosody_stats"] = self._prosody_stats
+        if self._prosody_span_stats is not None:
+            out["prosody_span_stats"] = self._prosody_span_stats
         out["mel"] = [mel_packed[b0:b0 + n] for b0, n in zip(rag_out.begins, rag_out.lengths)]
         for key, src in (("durations", d), ("pitch", p), ("energy", en)):
             out[key] = [src[b0:b0 + n] for b0, n in zip(rag_p.begins, rag_p.lengths)]

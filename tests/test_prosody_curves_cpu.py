@@ -1,0 +1,336 @@
+"""Per-phoneme prosody curves without a GPU: the float64 restatement (tests/prosody_curves_ref.py) against the oracle and on hand-made
+vectors, word_spans / emphasis / resolve_curves, header / binding / library agreement, the stage entries' argument checks, and
+synthesize_grid's fifth axis on a stub pipeline."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import ims_toucan_prosody_variance_amd  # noqa: F401
+from ims_toucan_prosody_variance_amd import build, capi, interface, prosody
+from ims_toucan_prosody_variance_amd.phonemes import phones_to_features
+from ims_toucan_prosody_variance_amd.prosody import Span
+from oracle import toucan_oracle as orc
+from tests import abi_emulator, prosody_curves_ref as cref, prosody_ref as ref
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+PHONES_A = "~həlˈoʊ wˈɜːld~#"
+PHONES_B = "~tˈɛst~#"
+PHONES_C = "~hi, ðɛɹ. aɪ? noʊ!~#"
+EPS32 = 2.0 ** -23
+
+
+def _random_batch(lengths, seed, unvoiced=()):
+    rng = np.random.default_rng(seed)
+    R = sum(lengths)
+    text = np.zeros((R, 62), dtype=np.float32)
+    text[:, ref.F_VOICED] = rng.random(R) < 0.6
+    text[:, ref.F_PHONEME] = rng.random(R) < 0.8
+    text[:, ref.F_WORD_BOUNDARY] = rng.random(R) < 0.15
+    text[:, ref.F_SILENCE] = rng.random(R) < 0.2
+    b0 = 0
+    for u, n in enumerate(lengths):
+        if u in unvoiced:
+            text[b0:b0 + n, ref.F_VOICED] = 0
+        b0 += n
+    pitch = (0.3 + 0.5 * rng.standard_normal(R)).astype(np.float32)
+    energy = (0.5 + 0.4 * rng.standard_normal(R)).astype(np.float32)
+    dur = rng.integers(0, 13, R).astype(np.int64)
+    return text, pitch, energy, dur
+
+
+def test_restatement_with_constant_tables_equals_the_oracle_per_utterance():
+    """A table constant over an utterance at (c_d, c_p, c_e, 0, 0) with no scales == oracle.toucan_oracle.control on the utterance
+    alone with those scalars: durations equal, pitch and energy within (n + 6) eps (1 + |s|) max|v| (the bound
+    tests/test_prosody_scales_cpu.py derives for this expression), NaN where the oracle has NaN."""
+    lengths = [1, 7, 33, 12, 64]
+    consts = [(1.0, 1.3, 1.0), (0.9, 1.0, 0.8), (1.2, 1.5, 1.0), (1.0, 1.0, 1.0), (1.5, 0.6, 2.0)]
+    text, pitch, energy, dur = _random_batch(lengths, 11, unvoiced=(2,))
+    gp, ge, gd = cref.control(text, pitch, energy, dur, lengths, None, cref.constant(lengths, consts))
+    b0 = 0
+    for u, n in enumerate(lengths):
+        sl = slice(b0, b0 + n)
+        op, oe, od = orc.control(torch.from_numpy(text[sl]), torch.from_numpy(pitch[sl]), torch.from_numpy(energy[sl]), torch.from_numpy(dur[sl]),
+                                 *[float(np.float32(c)) for c in consts[u]], 1.0)
+        assert np.array_equal(gd[sl], od.numpy()), u
+        for got, want, raw, s in ((gp[sl], op.numpy(), pitch[sl], consts[u][1]), (ge[sl], oe.numpy(), energy[sl], consts[u][2])):
+            assert np.array_equal(np.isnan(got), np.isnan(want)), u
+            tol = (n + 6) * EPS32 * (1 + abs(float(s))) * float(np.abs(raw).max())
+            ok = ~np.isnan(want)
+            assert np.all(np.abs(got[ok] - want[ok]) <= tol), (u, float(np.abs(got[ok] - want[ok]).max()), tol)
+        b0 += n
+    assert np.isnan(gp[8:41]).all()  # utterance 2 has no voiced phoneme and a constant pitch scale of 1.5: the mean of nothing
+    # scales times a neutral table == the per-utterance restatement, exactly (the same float64 arithmetic)
+    scales = np.float32([(1.0, 1.3, 1.0, 0.7), (0.9, 1.0, 0.8, 1.0), (1.2, 1.5, 1.0, 1.3), (1.0, 1.0, 1.0, 1.0), (1.5, 0.6, 2.0, 0.5)])
+    for a, b in zip(cref.control(text, pitch, energy, dur, lengths, scales, cref.neutral(sum(lengths))), ref.control(text, pitch, energy, dur, lengths, scales)):
+        assert np.array_equal(a, b, equal_nan=True)
+
+
+def _plain(n):
+    """n rows that the overrides leave alone: voiced phonemes, no boundary, no silence."""
+    text = np.zeros((n, 62), dtype=np.float32)
+    text[:, ref.F_VOICED] = text[:, ref.F_PHONEME] = 1
+    return text
+
+
+def test_hand_made_vectors():
+    text = _plain(6)
+    pitch = np.float32([1.0, 2.0, 0.0, 4.0, 0.5, 3.0])   # (a zero entry that is no override: a predicted 0)
+    energy = np.float32([0.5, 1.5, 2.5, 0.0, 1.0, 2.0])
+    dur = np.array([3, 5, 2, 7, 1, 4])
+    # an all-neutral table changes nothing
+    p, e, d = cref.control_one(text, pitch, energy, dur, None, cref.neutral(6))
+    assert np.array_equal(p, pitch) and np.array_equal(e, energy) and np.array_equal(d, dur)
+    # one emphasised span leaves the other rows' bits alone
+    table, _, counts = prosody.resolve_curves([6], [[Span(1, 3, duration=1.5, pitch=2.0, energy=0.5)]])
+    p, e, d = cref.control_one(text, pitch, energy, dur, None, table)
+    keep = [0, 3, 4, 5]
+    assert np.array_equal(p[keep], pitch[keep]) and np.array_equal(e[keep], energy[keep]) and np.array_equal(d[keep], dur[keep]) and counts == [1]
+    avg_p, avg_e = pitch[pitch != 0].astype(np.float64).mean(), energy[energy != 0].astype(np.float64).mean()
+    assert avg_p == 2.1 and avg_e == 1.5
+    assert p[1] == (2.0 - avg_p) * 2.0 + avg_p and p[2] == 0.0  # (the zero lands at avg (1 - 2) < 0: clamped back to 0)
+    assert e[1] == 1.5 and e[2] == (2.5 - avg_e) * 0.5 + avg_e
+    assert d.tolist() == [3, 8, 3, 7, 1, 4]  # rint(7.5) = 8, rint(3.0) = 3
+    # the reference's quirk: a zero inside a span scaled below 1 becomes avg (1 - es)
+    p, _, _ = cref.control_one(text, pitch, energy, dur, None, prosody.resolve_curves([6], [[Span(2, 3, pitch=0.5)]])[0])
+    assert p[2] == avg_p * 0.5 and np.array_equal(np.delete(p, 2), np.delete(pitch, 2))
+    # an offset on a zero entry leaves it 0; an offset that drives a value negative clamps to 0; others are shifted
+    table = prosody.resolve_curves([6], [[Span(0, 6, pitch_offset=-0.75, energy_offset=0.25)]])[0]
+    p, e, d = cref.control_one(text, pitch, energy, dur, None, table)
+    assert p.tolist() == [0.25, 1.25, 0.0, 3.25, 0.0, 2.25] and e.tolist() == [0.75, 1.75, 2.75, 0.0, 1.25, 2.25] and np.array_equal(d, dur)
+    # the offset comes after the scale and sees its result: a value the scale clamped to 0 stays 0
+    table = prosody.resolve_curves([6], [[Span(4, 5, pitch=3.0, pitch_offset=1.0)]])[0]
+    p, _, _ = cref.control_one(text, pitch, energy, dur, None, table)
+    assert (0.5 - avg_p) * 3.0 + avg_p < 0 and p[4] == 0.0
+    # overlapping spans compose in list order: factors multiply, offsets add, in float32
+    a, b = Span(0, 4, duration=1.1, pitch=1.3, energy=0.7, pitch_offset=0.1), Span(2, 6, duration=0.9, pitch=0.7, energy=1.3, pitch_offset=0.2, energy_offset=-0.3)
+    table, ranges, counts = prosody.resolve_curves([6], [[a, b]])
+    f = np.float32
+    assert table.dtype == np.float32 and ranges.tolist() == [[0, 4], [2, 6]] and counts == [2]
+    assert np.array_equal(table[0], f([1.1, 1.3, 0.7, 0.1, 0.0])) and np.array_equal(table[5], f([0.9, 0.7, 1.3, 0.2, -0.3]))
+    assert np.array_equal(table[2], [f(1.1) * f(0.9), f(1.3) * f(0.7), f(0.7) * f(1.3), f(0.1) + f(0.2), f(0.0) + f(-0.3)])
+    swapped = prosody.resolve_curves([6], [[b, a]])
+    assert swapped[1].tolist() == [[2, 6], [0, 4]]
+    # the utterance's scales multiply the table: S.pitch 2 on a row at 0.5 is neutral for that row (es == 1: not written)
+    p, _, _ = cref.control_one(text, pitch, energy, dur, (1.0, 2.0, 1.0, 1.0), prosody.resolve_curves([6], [[Span(1, 2, pitch=0.5)]])[0])
+    assert p[1] == pitch[1] and p[3] == (4.0 - avg_p) * 2.0 + avg_p and p[0] == 0.0  # (row 0 lands at -0.1: clamped)
+
+
+def test_word_spans_and_emphasis_on_the_fixture_strings():
+    fa, fb, fc = (phones_to_features(s) for s in (PHONES_A, PHONES_B, PHONES_C))
+    assert prosody.word_spans(fa) == [(1, 6), (7, 11)]  # ~ | h ə l oʊ (5 rows: o, ʊ) | space | w ɜː l d | ~ #
+    assert prosody.word_spans(fb) == [(1, 5)]
+    assert prosody.word_spans(fc) == [(1, 3), (4, 7), (9, 11), (13, 16)]  # the word boundary, ".", "?" and "!~#" all break a run
+    assert prosody.word_spans(torch.from_numpy(fa)) == prosody.word_spans(fa)
+    assert prosody.word_spans(np.zeros((0, 62), dtype=np.float32)) == [] and prosody.word_spans(np.ones((3, 62), dtype=np.float32)) == [(0, 3)]
+    for feats in (fa, fb, fc):  # the rule: maximal runs of feature 15, which no boundary / silence / punctuation row has
+        inside = np.zeros(len(feats), dtype=bool)
+        for a, b in prosody.word_spans(feats):
+            inside[a:b] = True
+        assert np.array_equal(inside, feats[:, 15] == 1)
+        assert not (feats[inside][:, [16, 21]] == 1).any() and not (feats[inside][:, 17:21] == 1).any()
+    spans = prosody.emphasis(fa, [1], duration=1.25, pitch=1.5, energy=1.1, pitch_offset=0.2)
+    assert len(spans) == 1 and (spans[0].start, spans[0].stop) == (7, 11) and spans[0].values() == (1.25, 1.5, 1.1, 0.2, 0.0)
+    assert [(s.start, s.stop) for s in prosody.emphasis(fc, [3, 0])] == [(13, 16), (1, 3)]
+    with pytest.raises(ValueError, match="word 2"):
+        prosody.emphasis(fa, [2])
+    assert prosody.CURVE_COLUMNS == ("duration", "pitch", "energy", "pitch_offset", "energy_offset")
+
+
+def test_resolve_curves_and_its_errors():
+    assert prosody.resolve_curves([3, 4], None) is None and prosody.resolve_curves([3, 4], [None, None]) is None
+    arr = np.float64([[1.5, 1.0, 1.0, 0.0, 0.0]] * 4)
+    table, ranges, counts = prosody.resolve_curves([3, 4, 2], [[Span(1, 3, pitch=2.0), Span(0, 0)], arr, None])
+    assert table.dtype == np.float32 and table.shape == (9, 5) and ranges.dtype == np.int32 and ranges.tolist() == [[1, 3], [0, 0]] and counts == [2, 0, 0]
+    assert np.array_equal(table[:3], np.float32([[1, 1, 1, 0, 0], [1, 2, 1, 0, 0], [1, 2, 1, 0, 0]]))
+    assert np.array_equal(table[3:7], np.float32(arr)) and np.array_equal(table[7:], cref.neutral(2))
+    assert prosody.resolve_curves([4], [torch.from_numpy(arr)])[0].tolist() == np.float32(arr).tolist()
+    _, ranges, counts = prosody.resolve_curves([3, 4], [None, [Span(2, 4)]])
+    assert ranges.tolist() == [[5, 7]] and counts == [0, 1]  # packed rows
+    with pytest.raises(ValueError, match="one entry per utterance"):
+        prosody.resolve_curves([3, 4], [None])
+    with pytest.raises(ValueError, match=r"utterance 1: an array must be \[4, 5\]"):
+        prosody.resolve_curves([3, 4], [None, arr[:3]])
+    with pytest.raises(ValueError, match=r"utterance 0: an array must be \[3, 5\]"):
+        prosody.resolve_curves([3], [np.ones((3, 4))])
+    for bad in (Span(2, 5), Span(-1, 2), Span(3, 2)):
+        with pytest.raises(ValueError, match="utterance 1: span 1"):
+            prosody.resolve_curves([3, 4], [None, [Span(0, 1), bad]])
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="utterance 1, phoneme 2: duration"):
+            prosody.resolve_curves([3, 4], [None, [Span(2, 3, duration=bad)]])
+    for name in ("pitch", "energy", "pitch_offset", "energy_offset"):
+        with pytest.raises(ValueError, match=f"utterance 0, phoneme 1: {name} "):
+            prosody.resolve_curves([3], [[Span(1, 2, **{name: float("nan")})]])
+    worse = arr.copy()
+    worse[3, 4] = np.inf
+    with pytest.raises(ValueError, match="utterance 1, phoneme 3: energy_offset"):
+        prosody.resolve_curves([3, 4], [None, worse])
+    with pytest.raises(ValueError, match="utterance 0, phoneme 1: duration"):  # an empty span's values are checked too
+        prosody.resolve_curves([3], [[Span(1, 1, duration=0.0)]])
+    with pytest.raises(ValueError, match="utterance 0, phoneme 0: pitch "):  # two finite factors whose fp32 product is not
+        prosody.resolve_curves([2], [[Span(0, 2, pitch=3e38), Span(0, 1, pitch=10.0)]])
+    with pytest.raises(ValueError, match="at most 2"):
+        prosody.resolve_curves([2], [[Span(0, 1)] * 3])
+    # scalars of a call with curves: the table the _c entries take, None only for "no scales"
+    assert prosody.broadcast_scales(2) is None
+    assert prosody.broadcast_scales(2, 1.0, 1.3).tolist() == np.float32([[1.0, 1.3, 1.0, 1.0]] * 2).tolist()
+    assert prosody.broadcast_scales(2, [0.9, 1.0], 1.3).tolist() == np.float32([[0.9, 1.3, 1.0, 1.0], [1.0, 1.3, 1.0, 1.0]]).tolist()
+    with pytest.raises(ValueError, match="utterance 0"):
+        prosody.broadcast_scales(2, -1.0)
+
+
+def test_curves_header_binding_and_library_agree():
+    """include/toucan_prosody_curves.h, capi.CURVE_PROTOTYPES and the symbols libtoucan_hip.so exports are the same set, disjoint from
+    the other headers' tables; the macro is len(CURVE_COLUMNS); the ABI version stays."""
+    root = os.path.dirname(HERE)
+    strip = lambda name: re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", name), encoding="utf-8").read(), flags=re.S)
+    text = strip("toucan_prosody_curves.h")
+    declared = sorted(set(re.findall(r"\b(tts_[a-z0-9_]+)\s*\(", text)))
+    assert declared == sorted(capi.CURVE_PROTOTYPES) == ["tts_control_and_regulate_c", "tts_copy_prosody_span_stats", "tts_prosody_control_c"]
+    for other in os.listdir(os.path.join(root, "include")):
+        if other != "toucan_prosody_curves.h":
+            assert not set(declared) & set(re.findall(r"\b(tts_[a-z0-9_]+)\s*\(", strip(other))), other
+    tables = [getattr(capi, n) for n in dir(capi) if n.endswith("PROTOTYPES") and n != "CURVE_PROTOTYPES"]
+    assert len(tables) >= 8 and not any(set(declared) & set(t) for t in tables)
+    macros = dict(re.findall(r"#define\s+(TTS_PROSODY_[A-Z_]+)\s+(\d+)", text))
+    assert {k: int(v) for k, v in macros.items()} == {"TTS_PROSODY_CURVE_COLUMNS": capi.PROSODY_CURVE_COLUMNS}
+    assert capi.PROSODY_CURVE_COLUMNS == len(prosody.CURVE_COLUMNS) == len(prosody.CURVE_NEUTRAL) == 5
+    for arg_list, name in zip(re.findall(r"\bint\s+tts_[a-z0-9_]+\s*\((.*?)\)\s*;", text, flags=re.S), re.findall(r"\bint\s+(tts_[a-z0-9_]+)\s*\(", text)):
+        assert len(arg_list.split(",")) == len(capi.CURVE_PROTOTYPES[name][1]), name
+    assert "prosody_curves.hip" in build.SOURCES
+    build.build()
+    handle = capi.lib()
+    assert isinstance(handle, ctypes.CDLL)
+    for n in declared:
+        assert hasattr(handle, n) and getattr(handle, n).argtypes == capi.CURVE_PROTOTYPES[n][1], n
+    assert handle.tts_abi_version() == 15
+
+
+def test_stage_entries_check_their_arguments_without_a_gpu():
+    """tts_control_and_regulate_c / tts_copy_prosody_span_stats on a handle with no batch in flight, and the kernel entry's host
+    checks: error codes and messages, nothing enqueued."""
+    lib = capi.lib()
+    assert isinstance(lib, ctypes.CDLL)
+    h = ctypes.c_void_p()
+    cfg = capi.TtsConfig(1, 1, 0, 0, 0, 0.0)
+    assert lib.tts_create(ctypes.byref(cfg), ctypes.byref(h)) == 0
+    curves = (ctypes.c_float * 5)(1, 1, 1, 0, 0)
+    spans = (ctypes.c_int32 * 2)(0, 1)
+    assert lib.tts_control_and_regulate_c(h, None, curves, spans, 1, None, None) != 0 and b"tts_encoder" in lib.tts_last_error()
+    assert lib.tts_control_and_regulate_c(h, None, None, None, 0, None, None) != 0 and b"tts_control_and_regulate_c" in lib.tts_last_error()
+    out = (ctypes.c_float * 8)()
+    assert lib.tts_copy_prosody_span_stats(h, out, out, None) != 0 and b"tts_control_and_regulate_c" in lib.tts_last_error()
+    assert lib.tts_copy_prosody_stats(h, out, out, None) != 0
+    assert lib.tts_prosody_control_c(None, 62, None, None, None, None, None, 0, None, None, None) == 0  # (an empty batch launches nothing)
+    assert lib.tts_prosody_control_c(None, 62, None, None, None, None, None, 2, None, None, None) != 0 and b"null" in lib.tts_last_error()
+    assert lib.tts_prosody_control_c(None, 62, None, None, None, None, None, -1, None, None, None) != 0 and b"negative" in lib.tts_last_error()
+    assert lib.tts_destroy(h) == 0
+
+
+@pytest.fixture(scope="module")
+def models_dir(tmp_path_factory):
+    d = tmp_path_factory.mktemp("Models")
+    interface.write_fixture_checkpoints(str(d), n_lang=20)
+    return str(d)
+
+
+@pytest.fixture()
+def tts(monkeypatch, models_dir):
+    abi_emulator.install(monkeypatch)
+    monkeypatch.setattr(interface, "MODELS_DIR", models_dir)
+    return interface.ToucanTTSInterface(device="cpu", tts_model_path="Meta", faster_vocoder=True)
+
+
+def test_interface_validates_curves_before_anything_runs(tts):
+    with pytest.raises(ValueError, match="distributed"):
+        tts.synthesize_batch([PHONES_A, PHONES_B], prosody_curves=[None, [Span(0, 2, pitch=1.2)]], distributed=True)
+    with pytest.raises(ValueError, match="one entry per utterance"):
+        tts.synthesize_batch([PHONES_A, PHONES_B], prosody_curves=[None])
+    with pytest.raises(ValueError, match="utterance 1: span 0"):
+        tts.synthesize_batch([PHONES_A, PHONES_B], prosody_curves=[None, [Span(0, 8)]])  # (PHONES_B has 7 phonemes)
+    with pytest.raises(ValueError, match="utterance 0, phoneme 7: duration"):
+        tts.synthesize_batch([PHONES_A], prosody_curves=[[Span(7, 11, duration=-1.0)]])
+    with pytest.raises(ValueError, match="utterance 1"):  # (the alternative, in a grid)
+        tts.synthesize_grid(PHONES_B, curves=[None, np.ones((3, 5))])
+    with pytest.raises(ValueError):
+        tts.synthesize_grid(PHONES_B, curves=[])
+    assert tts.last_prosody_stats is None and tts.last_prosody_span_stats is None
+
+
+class StubPipe:
+    """Stands in for native.NativePipeline.forward: two frames per variant, the wave of the k-th variant it ever saw filled with k, the
+    variant's four scales in its statistics rows, and per Span one span block that starts with (start, stop)."""
+
+    def __init__(self):
+        self.calls, self.seen = [], 0
+
+    def forward(self, phones, emb, lang_ids, z_noise=None, durations=None, pitch=None, energy=None, prosody_curves=None, **kw):
+        n = len(phones)
+        table = prosody.resolve_scales(n, **kw)
+        assert table is not None and prosody_curves is not None and len(prosody_curves) == n
+        self.calls.append(dict(n=n, z=z_noise, table=table, curves=list(prosody_curves)))
+        resolved = prosody.resolve_curves([int(p.shape[0]) for p in phones], prosody_curves)
+        ctab, ranges, counts = resolved if resolved is not None else (None, np.zeros((0, 2), dtype=np.int32), None)
+        wav = torch.cat([torch.full((768,), float(self.seen + i)) for i in range(n)])
+        self.seen += n
+        before = np.concatenate([table, np.zeros((n, 4), dtype=np.float32)], axis=1)
+        L = int(phones[0].shape[0])
+        local = np.concatenate([ranges % L, np.zeros((len(ranges), 6), dtype=np.int32)], axis=1).astype(np.float32)
+        per = [torch.zeros(1)] * n
+        out = dict(wav=wav, wav_spans=[(768 * i, 768) for i in range(n)], durations=per, pitch=per, energy=per, mel=per,
+                   prosody_stats=(before, before + 100))
+        if resolved is not None:  # (all None: the sequencers take the path without curves and report no span blocks)
+            out["prosody_span_stats"] = prosody.split_span_stats((local, local + 100), counts)
+        return out
+
+
+def test_grid_curves_are_the_slowest_axis_on_a_stub_pipeline(tts):
+    feats = phones_to_features(PHONES_A)
+    words = prosody.word_spans(feats)
+    curves = [prosody.emphasis(feats, [k]) for k in range(len(words))] + [None]
+    tts.pipe = stub = StubPipe()
+    D, P = (0.9, 1.1), (1.0, 1.5)
+    res = tts.synthesize_grid(PHONES_A, D, P, curves=curves)
+    scales = [(d, p, 1.0, 1.0) for d in D for p in P]
+    assert len(res) == 12 and [r["curve"] for r in res] == [0] * 4 + [1] * 4 + [2] * 4 and [r["scales"] for r in res] == scales * 3
+    assert [c["n"] for c in stub.calls] == [12] and [float(r["wave"][0]) for r in res] == list(range(12))
+    for r in res:
+        before, after = r["span_stats"]
+        if r["curve"] == 2:
+            assert before.shape == after.shape == (0, 8)
+        else:
+            assert before.shape == (1, 8) and tuple(before[0, :2]) == words[r["curve"]] and np.array_equal(after, before + 100)
+        assert np.array_equal(r["stats_before"][:4], np.float32(r["scales"]))
+    assert tts.last_prosody_span_stats is not None
+    # larger than MAX_FILE_BATCH: split, the alternatives follow their variants across the chunks, z_noise too
+    tts.pipe = stub = StubPipe()
+    axes = ((0.9, 1.0, 1.1), (1.0, 1.2, 1.5), (0.8, 1.0, 1.2))
+    z = [torch.full((80, 4), float(k)) for k in range(81)]
+    res = tts.synthesize_grid(PHONES_A, *axes, z_noise=z, curves=curves)
+    assert [c["n"] for c in stub.calls] == [32, 32, 17] and [r["curve"] for r in res] == [k for k in range(3) for _ in range(27)]
+    assert [r["scales"] for r in res] == prosody.grid(*axes) * 3 and [float(r["wave"][0]) for r in res] == list(range(81))
+    assert [float(zz[0, 0]) for c in stub.calls for zz in c["z"]] == list(range(81))
+    seen = [c for call in stub.calls for c in call["curves"]]
+    assert all(seen[i] is curves[i // 27] for i in range(81))
+    with pytest.raises(ValueError, match="z_noise"):
+        tts.synthesize_grid(PHONES_A, D, P, curves=curves, z_noise=z[:4])
+    # without curves the call and its result dicts are what they were
+    tts.pipe = StubPlain()
+    res = tts.synthesize_grid(PHONES_A, D, P)
+    assert len(res) == 4 and all(set(r) == {"scales", "wave", "frames", "stats_before", "stats_after"} for r in res)
+
+
+class StubPlain:
+    """A pipeline from before the keyword: it would raise on prosody_curves=."""
+
+    def forward(self, phones, emb, lang_ids, z_noise=None, durations=None, pitch=None, energy=None, **kw):
+        n = len(phones)
+        table = prosody.resolve_scales(n, **kw)  # (TypeError for any keyword but the four scales)
+        stats = np.concatenate([table, np.zeros((n, 4), dtype=np.float32)], axis=1)
+        per = [torch.zeros(1)] * n
+        return dict(wav=torch.zeros(768 * n), wav_spans=[(768 * i, 768) for i in range(n)], durations=per, pitch=per, energy=per, mel=per,
+                    prosody_stats=(stats, stats))
