@@ -59,6 +59,25 @@ struct WavenetCond {
 };
 int wavenet_layer_cond(const TtsWavenetDesc& d, const WavenetCond& c, hipStream_t st);
 
+// The WaveNet of one coupling block in one launch (wavenet.hip): h = start(x0) and the four layers; x in ([rows, >= 80] fp32, the
+// packed rows of the squeezed layout; only x0 = columns 0 .. 79 is read), the block's skip sum out ([rows, 192] fp32).  The start
+// conv as packed for tts_conv1d's 16-bit path ([1][cin_pad / 8][w0_n][8], only its first 192 columns are used), the layers'
+// weights and the conditioning as for wavenet_layer_cond; layer i uses conditioning columns 384 i .. 384 i + 383.  The tile
+// table has wavenet_block_tile_rows() rows per tile.
+struct WavenetBlock {
+  const float* x; int ld_x;
+  float* skip; int ld_skip;
+  const void* w0; int w0_n; const float* b0;  // start: 80 -> 192
+  const void* w1[4]; const float* b1[4];      // in_layer: packed [5][24][384][8], bias [384]
+  const void* w2[4]; const float* b2[4];      // res_skip: packed [1][24][384][8] (last layer [1][24][192][8]), bias
+  const float* g; int ld_g;
+  const void* wc; int wc_n; const float* bc;
+  const TtsTile* tiles; int n_tiles; int tile_rows;
+  int compute;
+};
+int wavenet_block(const WavenetBlock& d, hipStream_t st);
+int wavenet_block_tile_rows();
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));

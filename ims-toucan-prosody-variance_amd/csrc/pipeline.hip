@@ -1312,19 +1312,12 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
   TTS_ALLOC(x, a, float, (size_t)RS * 160);
   TTS_TRY(hip_ok(hipMemcpyAsync(x, z_noise, (size_t)RS * 160 * 4, hipMemcpyDeviceToDevice, st), "flow noise"));
   TTS_ALLOC(hs, a, float, (size_t)RS * 2 * ATT);  // [hidden state | skip sum]
-  // 16-bit configurations: one launch per WaveNet layer (tts_wavenet_layer); the state ping-pongs between hs and hs2
+  // 16-bit configurations: one launch for the WaveNet of a block (wavenet_block: start conv and the four layers): it reads x0 and
+  // writes the block's skip sum into the second half of hs; the hidden state never leaves the chip
   const bool fused = !postflow_cond_buffer(h);
-  float* hs2 = nullptr;
-  TileTab t64;
-  if (fused) {
-    hs2 = arena_alloc<float>(a, (size_t)RS * 2 * ATT);
-    if (!hs2) {
-      set_error("tts_postflow: workspace exhausted");
-      return TTS_E_ARG;
-    }
-    TTS_TRY(tiles_of(h, ls, 64, st, &t64));
-  }
-  // the fused layers compute their conditioning columns themselves (wavenet_layer_cond): no acts, no cond buffer
+  TileTab tblk;
+  if (fused) TTS_TRY(tiles_of(h, ls, wavenet_block_tile_rows(), st, &tblk));
+  // the fused layers compute their conditioning columns themselves: no acts, no cond buffer
   char* acts = nullptr;
   float* cond = nullptr;
   if (!fused) {
@@ -1341,30 +1334,35 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
   for (int b = 17; b >= 0; --b) {
     const auto& f = m.flow[b];
     const ConvW& cnd = f.cond;
-    TTS_TRY(conv(h, f.start, T2(x, 160), T2(hs, 2 * ATT), ls, st));            // h = start(x0); the zero half clears the skip sum
-    if (!fused) TTS_TRY(conv(h, cnd, T2(g, 2 * ATT), T2(cond, 8 * ATT), ls, st));  // squeeze of g = re-view [RS, 384]
-    float* cur = hs;
-    for (int i = 0; i < 4; ++i) {
-      const ConvW &inl = m.flowgrp[b / 4].inl[i], &rs = m.flowgrp[b / 4].res_skip[i];
-      if (fused) {
-        float* nxt = cur == hs ? hs2 : hs;
-        TtsWavenetDesc w;
-        memset(&w, 0, sizeof(w));
-        w.hs_in = cur; w.ld_in = 2 * ATT; w.hs_out = nxt; w.ld_out = 2 * ATT;
-        w.w1 = inl.w16; w.b1 = inl.bias; w.w2 = rs.w16; w.b2 = rs.bias;
-        w.cout2 = rs.cout; w.compute = inl.compute16;
-        w.tiles = t64.dev; w.n_tiles = t64.n; w.tile_rows = 64;
-        TTS_CHECK_ARG(cnd.w16 && cnd.mode == TTS_MODE_LINEAR && cnd.compute16 == inl.compute16 && cnd.cin == 2 * ATT && cnd.cin_pad == 2 * ATT && cnd.cout == 8 * ATT &&
-                          cnd.taps == 1 && cnd.wn >= 8 * ATT,
-                      "tts_postflow: flow.%d.cond is not a 16-bit 1-tap 384 -> 1536 conv", b);
-        const WavenetCond wc = {g, 2 * ATT, cnd.w16, cnd.wn, i * 2 * ATT, cnd.bias};
-        // in-layer, conditioning and res/skip products; state in and out, g, weights
-        TTS_TRY(prof_launch(h, "wavenet_layer", 2.0 * live_rows * (ATT * 5 * 2 * ATT + 2 * ATT * 2 * ATT + (double)ATT * rs.cout),
-                            live_rows * 4.0 * (2 * ATT + rs.cout + 2 * ATT) + 2.0 * (5 * ATT * 2 * ATT + 2 * ATT * 2 * ATT + ATT * rs.cout),
-                            live_rows * rs.cout, st, [&] { return wavenet_layer_cond(w, wc, st); }));
-        cur = nxt;
-        continue;
+    if (!fused) {
+      TTS_TRY(conv(h, f.start, T2(x, 160), T2(hs, 2 * ATT), ls, st));          // h = start(x0); the zero half clears the skip sum
+      TTS_TRY(conv(h, cnd, T2(g, 2 * ATT), T2(cond, 8 * ATT), ls, st));        // squeeze of g = re-view [RS, 384]
+    }
+    if (fused) {
+      TTS_CHECK_ARG(f.start.w16 && f.start.mode == TTS_MODE_LINEAR && f.start.compute16 == cnd.compute16 && f.start.cin == 80 && f.start.taps == 1 && f.start.wn >= ATT,
+                    "tts_postflow: flow.%d.start is not a 16-bit 1-tap 80 -> 192 conv", b);
+      TTS_CHECK_ARG(cnd.w16 && cnd.mode == TTS_MODE_LINEAR && cnd.cin == 2 * ATT && cnd.cin_pad == 2 * ATT && cnd.cout == 8 * ATT && cnd.taps == 1 && cnd.wn >= 8 * ATT,
+                    "tts_postflow: flow.%d.cond is not a 16-bit 1-tap 384 -> 1536 conv", b);
+      WavenetBlock w;
+      memset(&w, 0, sizeof(w));
+      w.x = x; w.ld_x = 160; w.skip = skip; w.ld_skip = 2 * ATT;
+      w.w0 = f.start.w16; w.w0_n = f.start.wn; w.b0 = f.start.bias;
+      w.g = g; w.ld_g = 2 * ATT; w.wc = cnd.w16; w.wc_n = cnd.wn; w.bc = cnd.bias;
+      w.tiles = tblk.dev; w.n_tiles = tblk.n; w.tile_rows = wavenet_block_tile_rows();
+      w.compute = cnd.compute16;
+      for (int i = 0; i < 4; ++i) {
+        const ConvW &inl = m.flowgrp[b / 4].inl[i], &rs = m.flowgrp[b / 4].res_skip[i];
+        TTS_CHECK_ARG(inl.w16 && rs.w16 && inl.compute16 == cnd.compute16 && rs.cout == (i < 3 ? 2 * ATT : ATT), "tts_postflow: flow.%d layer %d is not a 16-bit WaveNet layer", b, i);
+        w.w1[i] = inl.w16; w.b1[i] = inl.bias; w.w2[i] = rs.w16; w.b2[i] = rs.bias;
       }
+      // start, and four layers' in-layer, conditioning and res/skip products (the halo's repeated rows are not counted); x0 in, skip
+      // out, g, weights
+      TTS_TRY(prof_launch(h, "wavenet_block", 2.0 * live_rows * (80.0 * ATT + 4.0 * (ATT * 5 * 2 * ATT + 2 * ATT * 2 * ATT) + 3.0 * ATT * 2 * ATT + (double)ATT * ATT),
+                          live_rows * 4.0 * (80 + ATT + 2 * ATT) + 2.0 * (80.0 * ATT + 4.0 * (5 * ATT * 2 * ATT + 2 * ATT * 2 * ATT) + 3.0 * ATT * 2 * ATT + (double)ATT * ATT),
+                          live_rows * ATT, st, [&] { return wavenet_block(w, st); }));
+    }
+    for (int i = 0; i < 4 && !fused; ++i) {
+      const ConvW &inl = m.flowgrp[b / 4].inl[i], &rs = m.flowgrp[b / 4].res_skip[i];
       ConvOpt oi;
       oi.preadd = cond + (size_t)i * 2 * ATT;
       oi.ld_preadd = 8 * ATT;
@@ -1377,7 +1375,7 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
     oe.aux = x + 80;
     oe.ld_aux = 160;
     oe.fp32_only = true;
-    TTS_TRY(conv(h, f.end, T2(cur + ATT, 2 * ATT), T2(x + 80, 160), ls, st, oe));  // (four fused layers end in `hs` again)
+    TTS_TRY(conv(h, f.end, T2(skip, 2 * ATT), T2(x + 80, 160), ls, st, oe));
     TTS_TRY(tts_glow_invconv_actnorm(x, 160, RS, 160, f.winv, f.an_bias, f.an_logs, st));
   }
   h->mel = x;  // unsqueeze = re-view [2 RS, 80]

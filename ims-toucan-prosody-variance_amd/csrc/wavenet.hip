@@ -327,6 +327,311 @@ __global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc
   }
 }
 
+// ---- One coupling block's WaveNet (the start conv and its four layers) in one launch -----------------------------------------
+// h = start(x0) is computed in the workgroup (80 -> 192, five k-steps), then the layer body above, looped: the hidden state and the skip sum stay in the registers of the wavefronts that own their output
+// channels in the res/skip product (waves 0, 1: h; waves 2, 3: skip), the next layer's 16-bit window is written straight from
+// the res/skip epilogue, the squeezed g is staged once for the four conditioning products, and the weight stream runs on from
+// one layer into the next.  Nothing but the block's skip sum is written.  Halo by recomputation: a workgroup computes the 64 rows
+// row0 - 8 .. row0 + 55 through all four layers (each 5-tap layer costs 2 rows a side) and stores the central 48; the tile table
+// has 48-row tiles.  In every layer's window the rows outside the utterance are zeros (the per-layer form's zero padding), also
+// where they lie inside the computed range.  Acts have a buffer of their own, so a layer needs two barriers: the window is
+// complete; acts are complete.  Every product keeps the per-layer kernel's k order and epilogue expressions: same bits.
+// The last layer (192 res/skip columns) keeps the ownership of the others - waves 2, 3 own the skip blocks, waves 0, 1 repeat
+// them and drop the result - so the skip sum never changes registers.
+namespace {
+constexpr int WB_OUT = 48;   // rows stored per workgroup
+constexpr int WB_HALO = 8;   // 4 layers x 2 rows
+constexpr int WB_CIN = 80;   // channels of x0, the start conv's input
+constexpr size_t WB_AS_BYTES = (size_t)WN_BM * WN_XP * 2;
+constexpr size_t WB_LDS_BYTES = WN_XS_BYTES + WB_AS_BYTES + WN_GS_BYTES;
+static_assert(WB_OUT + 2 * WB_HALO == WN_BM, "stored rows plus the halo are the computed tile");
+}  // namespace
+
+template <bool F16>
+__global__ __launch_bounds__(256) void wavenet_block_kernel(const WavenetBlock d) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  unsigned short* xs = reinterpret_cast<unsigned short*>(lds_raw);                               // [68][XP] window of h
+  unsigned short* as = reinterpret_cast<unsigned short*>(lds_raw + WN_XS_BYTES);                 // [64][XP] acts
+  unsigned short* gs = reinterpret_cast<unsigned short*>(lds_raw + WN_XS_BYTES + WB_AS_BYTES);  // [64][GP] squeezed g
+  const TtsTile tile = d.tiles[blockIdx.x];
+  const int c0 = tile.row0 - WB_HALO;  // first computed row
+  const int tid = threadIdx.x, lane = tid & 63, lrow = lane & 31, lk = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int P0 = (wave * 5 + 1) / 3, P1 = wave < 2 ? 1 : 4, fP = wave & 1, fQ = fP ^ 1;
+  auto clamp_row = [&](int gr) __attribute__((always_inline)) { return gr < tile.seq_begin ? tile.seq_begin : (gr >= tile.seq_end ? tile.seq_end - 1 : gr); };
+  auto pick = [&](auto (&arr)[4], int i) __attribute__((always_inline)) { return i == 0 ? arr[0] : (i == 1 ? arr[1] : (i == 2 ? arr[2] : arr[3])); };
+
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 wr[WN_DEPTH][WN_L];  // the weight stream of wavenet_layer_kernel
+  const char *q0, *q1, *q2, *q3;
+  size_t qs;
+  auto request = [&](int slot) __attribute__((always_inline)) {
+    TTS_GLOAD128(wr[slot][0], q0);
+    TTS_GLOAD128(wr[slot][1], q1);
+    TTS_GLOAD128(wr[slot][2], q2);
+    TTS_GLOAD128(wr[slot][3], q3);
+    q0 += qs; q1 += qs; q2 += qs; q3 += qs;
+  };
+  auto arrive = [&](int slot) __attribute__((always_inline)) {
+    TTS_WAIT_VM((WN_DEPTH - 1) * WN_L);
+    TTS_PIN(wr[slot][0]);
+    TTS_PIN(wr[slot][1]);
+    TTS_PIN(wr[slot][2]);
+    TTS_PIN(wr[slot][3]);
+  };
+  auto stream_pairs = [&](const void* w, int n, int col0) __attribute__((always_inline)) {
+    const char* b = reinterpret_cast<const char*>(w) + ((size_t)lk * n + col0 + lrow) * 16;
+    q0 = b + P0 * 512; q1 = q0 + WN_H * 16; q2 = b + P1 * 512; q3 = q2 + WN_H * 16;
+    qs = (size_t)n * 32;
+  };
+  auto stream_res_skip = [&](const void* w, int n, int cb) __attribute__((always_inline)) {  // blocks cb .. cb + 2
+    const char* b = reinterpret_cast<const char*>(w) + ((size_t)lk * n + lrow) * 16 + cb * 512;
+    q0 = b; q1 = b + 512; q2 = b + 1024; q3 = q2;
+    qs = (size_t)n * 32;
+  };
+  auto publish = [&]() __attribute__((always_inline)) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  };
+
+  stream_pairs(d.w1[0], 2 * WN_H, 0);
+#pragma unroll
+  for (int u = 0; u < WN_DEPTH; ++u) request(u);
+
+  // ---- the tile's g rows -> 16-bit, once for the four layers (rows outside the utterance read its nearest row: their results
+  // are never stored)
+  {
+    constexpr int GQ4 = WN_G / 4, GPER = WN_BM * GQ4 / 256, PER = 8;
+    static_assert(GPER % PER == 0, "g staging trips");
+#pragma unroll 1
+    for (int p0 = 0; p0 < GPER; p0 += PER) {
+      float4 v[PER];
+#pragma unroll
+      for (int p = 0; p < PER; ++p) {
+        const int e = tid + (p0 + p) * 256, r = e / GQ4, c4 = (e % GQ4) * 4;
+        v[p] = *reinterpret_cast<const float4*>(d.g + (size_t)clamp_row(c0 + r) * d.ld_g + c4);
+      }
+#pragma unroll
+      for (int p = 0; p < PER; ++p) {
+        const int e = tid + (p0 + p) * 256, r = e / GQ4, c4 = (e % GQ4) * 4;
+        *reinterpret_cast<uint2*>(gs + r * WN_GP + c4) = make_uint2(pack16<F16>(v[p].x, v[p].y), pack16<F16>(v[p].z, v[p].w));
+      }
+    }
+  }
+  // ---- h = start(x0) for the 64 computed rows, in the arithmetic of the stand-alone conv (16-bit 32x32x16, k ascending over the
+  // 80 channels of x0, (acc + bias) + 0): waves 0, 1 compute the blocks they own in the res/skip product straight into the state
+  // registers and write the first layer's window (zero outside the utterance).  Window rows 0, 1, 66, 67 reach no stored row
+  // (the halo is 8 rows for the layers' 2 + 2 + 2 + 2): zeros.
+  // The state: st[2 i] = res/skip block 3 wave + i over frame block fP, st[2 i + 1] over fQ.  Waves 0, 1: h in fp32 (the residual
+  // input of every layer); waves 2, 3: the skip sum, which starts at zero.
+  f32x16 st[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) st[j][r] = 0.0f;
+  if (wave < 2) {
+    const float* xrP = d.x + (size_t)clamp_row(c0 + fP * 32 + lrow) * d.ld_x + lk * 8;
+    const float* xrQ = d.x + (size_t)clamp_row(c0 + fQ * 32 + lrow) * d.ld_x + lk * 8;
+    const char* wb = reinterpret_cast<const char*>(d.w0) + ((size_t)lk * d.w0_n + 96 * wave + lrow) * 16;
+#pragma unroll
+    for (int s = 0; s < WB_CIN / 16; ++s) {
+      const float4 p0 = *reinterpret_cast<const float4*>(xrP + 16 * s), p1 = *reinterpret_cast<const float4*>(xrP + 16 * s + 4);
+      const float4 r0 = *reinterpret_cast<const float4*>(xrQ + 16 * s), r1 = *reinterpret_cast<const float4*>(xrQ + 16 * s + 4);
+      const u32x4 uP = {pack16<F16>(p0.x, p0.y), pack16<F16>(p0.z, p0.w), pack16<F16>(p1.x, p1.y), pack16<F16>(p1.z, p1.w)};
+      const u32x4 uQ = {pack16<F16>(r0.x, r0.y), pack16<F16>(r0.z, r0.w), pack16<F16>(r1.x, r1.y), pack16<F16>(r1.z, r1.w)};
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const u32x4 wf = *reinterpret_cast<const u32x4*>(wb + (size_t)s * d.w0_n * 32 + i * 512);
+        st[2 * i] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, uP), st[2 * i]);
+        st[2 * i + 1] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, uQ), st[2 * i + 1]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int cb = 3 * wave + (j >> 1), t = ((j & 1) ? fQ : fP) * 32 + lrow, gr = c0 + t;
+      const bool inside = gr >= tile.seq_begin && gr < tile.seq_end;
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const int c = cb * 32 + 8 * rq + 4 * lk;
+        const float4 b = *reinterpret_cast<const float4*>(d.b0 + c);
+        const float v0 = (st[j][4 * rq] + b.x) + 0.0f, v1 = (st[j][4 * rq + 1] + b.y) + 0.0f;
+        const float v2 = (st[j][4 * rq + 2] + b.z) + 0.0f, v3 = (st[j][4 * rq + 3] + b.w) + 0.0f;
+        st[j][4 * rq] = v0; st[j][4 * rq + 1] = v1; st[j][4 * rq + 2] = v2; st[j][4 * rq + 3] = v3;
+        *reinterpret_cast<uint2*>(xs + (t + 2) * WN_XP + c) = inside ? make_uint2(pack16<F16>(v0, v1), pack16<F16>(v2, v3)) : make_uint2(0u, 0u);
+      }
+    }
+  } else {
+    constexpr int Q4 = WN_XP / 4;  // 8-byte pieces of a window row
+    for (int e = tid - 128; e < 4 * Q4; e += 128) {
+      const int r = e / Q4, row = r < 2 ? r : WN_BM + r;  // 0, 1, 66, 67
+      *reinterpret_cast<uint2*>(xs + row * WN_XP + (e % Q4) * 4) = make_uint2(0u, 0u);
+    }
+  }
+
+  f32x16 acc[6], accc[6];
+  auto xload = [&](bf16x8& xP, bf16x8& xQ, const unsigned short* xrow, int pitch) __attribute__((always_inline)) {
+    xP = *reinterpret_cast<const bf16x8*>(xrow + (fP * 32 + lrow) * pitch + lk * 8);
+    xQ = *reinterpret_cast<const bf16x8*>(xrow + (fQ * 32 + lrow) * pitch + lk * 8);
+  };
+  auto pair_step = [&](int slot, f32x16 (&a)[6], bf16x8& xP, bf16x8& xQ, const unsigned short* xnext, int pitch) __attribute__((always_inline)) {
+    const bf16x8 cP = xP, cQ = xQ;
+    xload(xP, xQ, xnext, pitch);
+    arrive(slot);
+    u32x4 wf[WN_L];
+#pragma unroll
+    for (int i = 0; i < WN_L; ++i) wf[i] = wr[slot][i];
+    a[0] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[0]), cP, a[0]);
+    a[1] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[0]), cQ, a[1]);
+    a[2] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[1]), cP, a[2]);
+    a[3] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[1]), cQ, a[3]);
+    a[4] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[2]), cP, a[4]);
+    a[5] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[3]), cP, a[5]);
+    request(slot);
+  };
+  bf16x8 xP, xQ;
+  auto window_at = [&](int s) __attribute__((always_inline)) {
+    s = s < WN_STEPS1 ? s : WN_STEPS1 - 1;
+    return xs + (s / (WN_H / 16)) * WN_XP + (s % (WN_H / 16)) * 16;
+  };
+
+#pragma unroll 1
+  for (int i = 0; i < 4; ++i) {
+    const float *b1 = pick(d.b1, i), *b2 = pick(d.b2, i);
+    const void* w2 = pick(d.w2, i);
+    const int n2 = i < 3 ? 2 * WN_H : WN_H, cbase = i < 3 ? 3 * wave : 3 * (wave & 1), ccol = i * 2 * WN_H;
+    publish();  // (1) the window is complete (first layer: and g)
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+    // ---- gated conv: tap-major, k ascending in 16-channel steps
+    xload(xP, xQ, window_at(0), WN_XP);
+#pragma unroll 1
+    for (int base = 0; base < WN_STEPS1; base += WN_DEPTH) {
+      if (base == WN_STEPS1 - WN_DEPTH) stream_pairs(d.wc, d.wc_n, ccol);
+#pragma unroll
+      for (int u = 0; u < WN_DEPTH; ++u) pair_step(u, acc, xP, xQ, window_at(base + u + 1), WN_XP);
+    }
+    // ---- cond = cond_conv(g)[this layer's 384 columns]
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accc[j][r] = 0.0f;
+    xload(xP, xQ, gs, WN_GP);
+#pragma unroll 1
+    for (int base = 0; base < WN_STEPSC; base += WN_DEPTH) {
+      if (base == WN_STEPSC - WN_DEPTH) stream_res_skip(w2, n2, cbase);
+#pragma unroll
+      for (int u = 0; u < WN_DEPTH; ++u) {
+        const int s1 = base + u + 1 < WN_STEPSC ? base + u + 1 : WN_STEPSC - 1;
+        pair_step(u, accc, xP, xQ, gs + s1 * 16, WN_GP);
+      }
+    }
+    // ---- acts = tanh(a + bias + cond) * sigmoid(g + bias + cond) -> LDS, 16-bit (the expressions of wavenet_layer_kernel)
+    {
+      auto gate = [&](const f32x16& aa, const f32x16& ag, const f32x16& ca, const f32x16& cg, int pb, int f) __attribute__((always_inline)) {
+        const int t = f * 32 + lrow;
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+          const int c = pb * 32 + 8 * rq + 4 * lk;
+          const float4 ba = *reinterpret_cast<const float4*>(b1 + c), bg = *reinterpret_cast<const float4*>(b1 + WN_H + c);
+          float pa[4], pg[4];
+          const float4 ea = *reinterpret_cast<const float4*>(d.bc + ccol + c), eg = *reinterpret_cast<const float4*>(d.bc + ccol + WN_H + c);
+          const float eav[4] = {ea.x, ea.y, ea.z, ea.w}, egv[4] = {eg.x, eg.y, eg.z, eg.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            pa[q] = (ca[4 * rq + q] + eav[q]) + 0.0f;
+            pg[q] = (cg[4 * rq + q] + egv[q]) + 0.0f;
+          }
+          const float bav[4] = {ba.x, ba.y, ba.z, ba.w}, bgv[4] = {bg.x, bg.y, bg.z, bg.w};
+          float v[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float av = aa[4 * rq + q] + bav[q] + pa[q], gvv = ag[4 * rq + q] + bgv[q] + pg[q];
+            const float th = 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * av)) - 1.0f;
+            v[q] = th * __builtin_amdgcn_rcpf(1.0f + __expf(-gvv));
+          }
+          *reinterpret_cast<uint2*>(as + t * WN_XP + c) = make_uint2(pack16<F16>(v[0], v[1]), pack16<F16>(v[2], v[3]));
+        }
+      };
+      gate(acc[0], acc[2], accc[0], accc[2], P0, fP);
+      gate(acc[1], acc[3], accc[1], accc[3], P0, fQ);
+      gate(acc[4], acc[5], accc[4], accc[5], P1, fP);
+#pragma unroll
+      for (int j = 0; j < 6; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+    }
+    publish();  // (2) acts are complete (and every wave is done with the window)
+    // ---- res / skip conv: acc[2 j] = block cbase + j over fP, acc[2 j + 1] over fQ
+    xload(xP, xQ, as, WN_XP);
+#pragma unroll 1
+    for (int base = 0; base < WN_STEPS2; base += WN_DEPTH) {
+      if (base == WN_STEPS2 - WN_DEPTH) {
+        if (i < 3) {  // the requests of this block are the first k-steps of the next layer
+          stream_pairs(pick(d.w1, i + 1), 2 * WN_H, 0);
+        } else {  // nothing follows: the tail re-requests the last k-step (unused)
+          q0 -= qs; q1 -= qs; q2 -= qs; q3 -= qs;
+          qs = 0;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < WN_DEPTH; ++u) {
+        const bf16x8 cP = xP, cQ = xQ;
+        const int s1 = base + u + 1 < WN_STEPS2 ? base + u + 1 : WN_STEPS2 - 1;
+        xload(xP, xQ, as + s1 * 16, WN_XP);
+        arrive(u);
+        u32x4 wf[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) wf[k] = wr[u][k];
+        acc[0] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[0]), cP, acc[0]);
+        acc[1] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[0]), cQ, acc[1]);
+        acc[2] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[1]), cP, acc[2]);
+        acc[3] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[1]), cQ, acc[3]);
+        acc[4] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[2]), cP, acc[4]);
+        acc[5] = mfma16<F16>(__builtin_bit_cast(bf16x8, wf[2]), cQ, acc[5]);
+        request(u);
+      }
+    }
+    // ---- state += res_skip + bias; waves 0, 1 write the next layer's window (zero outside the utterance)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int cb = cbase + (j >> 1), t = ((j & 1) ? fQ : fP) * 32 + lrow, gr = c0 + t;
+      const bool inside = gr >= tile.seq_begin && gr < tile.seq_end;
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const int c = cb * 32 + 8 * rq + 4 * lk;
+        const float4 b = *reinterpret_cast<const float4*>(b2 + c);
+        const float v0 = (acc[j][4 * rq] + b.x) + st[j][4 * rq], v1 = (acc[j][4 * rq + 1] + b.y) + st[j][4 * rq + 1];
+        const float v2 = (acc[j][4 * rq + 2] + b.z) + st[j][4 * rq + 2], v3 = (acc[j][4 * rq + 3] + b.w) + st[j][4 * rq + 3];
+        st[j][4 * rq] = v0; st[j][4 * rq + 1] = v1; st[j][4 * rq + 2] = v2; st[j][4 * rq + 3] = v3;
+        if (i < 3 && wave < 2)
+          *reinterpret_cast<uint2*>(xs + (t + 2) * WN_XP + c) = inside ? make_uint2(pack16<F16>(v0, v1), pack16<F16>(v2, v3)) : make_uint2(0u, 0u);
+      }
+    }
+  }
+  TTS_WAIT_VM(0);  // drain the tail requests: their destination registers stay allocated (pinned) until here
+#pragma unroll
+  for (int u = 0; u < WN_DEPTH; ++u) {
+    TTS_PIN(wr[u][0]);
+    TTS_PIN(wr[u][1]);
+    TTS_PIN(wr[u][2]);
+    TTS_PIN(wr[u][3]);
+  }
+  // ---- the block's skip sum: the central rows of the tile, inside the utterance
+  if (wave >= 2) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int cb = 3 * (wave - 2) + (j >> 1), t = ((j & 1) ? fQ : fP) * 32 + lrow, row = c0 + t;
+      if (t < WB_HALO || t >= WB_HALO + WB_OUT || row >= tile.seq_end) continue;
+      float* orow = d.skip + (size_t)row * d.ld_skip + cb * 32 + 4 * lk;
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq)
+        *reinterpret_cast<float4*>(orow + 8 * rq) = make_float4(st[j][4 * rq], st[j][4 * rq + 1], st[j][4 * rq + 2], st[j][4 * rq + 3]);
+    }
+  }
+}
+
 namespace {
 int wavenet_launch(const TtsWavenetDesc& d, const WavenetCond* c, hipStream_t st) {
   TTS_CHECK_ARG(d.hs_in && d.hs_out && d.w1 && d.b1 && d.w2 && d.b2 && d.tiles, "wavenet_layer: null pointer");
@@ -366,6 +671,36 @@ int wavenet_launch(const TtsWavenetDesc& d, const WavenetCond* c, hipStream_t st
   return launch_status("wavenet_layer");
 }
 }  // namespace
+
+int wavenet_block_tile_rows() { return WB_OUT; }
+
+int wavenet_block(const WavenetBlock& d, hipStream_t st) {
+  TTS_CHECK_ARG(d.x && d.w0 && d.b0 && d.skip && d.g && d.wc && d.bc && d.tiles, "wavenet_block: null pointer");
+  for (int i = 0; i < 4; ++i) {
+    TTS_CHECK_ARG(d.w1[i] && d.b1[i] && d.w2[i] && d.b2[i], "wavenet_block: null weights of layer %d", i);
+    TTS_CHECK_ARG(((uintptr_t)d.w1[i] & 15) == 0 && ((uintptr_t)d.w2[i] & 15) == 0 && ((uintptr_t)d.b1[i] & 15) == 0 && ((uintptr_t)d.b2[i] & 15) == 0,
+                  "wavenet_block: weights must be 16-byte aligned");
+  }
+  TTS_CHECK_ARG(d.compute == TTS_COMPUTE_BF16 || d.compute == TTS_COMPUTE_F16, "wavenet_block: 16-bit MFMA configurations only (compute %d)", d.compute);
+  TTS_CHECK_ARG(d.tile_rows == WB_OUT, "wavenet_block: tile table must use %d rows, got %d", WB_OUT, d.tile_rows);
+  TTS_CHECK_ARG(d.ld_x >= WB_CIN && (d.ld_x & 3) == 0 && d.ld_skip >= WN_H && (d.ld_skip & 3) == 0 && d.ld_g >= WN_G && (d.ld_g & 3) == 0 &&
+                    ((uintptr_t)d.x & 15) == 0 && ((uintptr_t)d.skip & 15) == 0 && ((uintptr_t)d.g & 15) == 0 && ((uintptr_t)d.wc & 15) == 0 && ((uintptr_t)d.bc & 15) == 0 &&
+                    ((uintptr_t)d.w0 & 15) == 0 && ((uintptr_t)d.b0 & 15) == 0,
+                "wavenet_block: rows, start and conditioning operands must be 16-byte aligned");
+  TTS_CHECK_ARG(d.w0_n >= WN_H, "wavenet_block: the start conv has %d packed columns, the hidden state %d", d.w0_n, WN_H);
+  TTS_CHECK_ARG(d.wc_n >= 8 * WN_H, "wavenet_block: %d conditioning columns, four layers need %d", d.wc_n, 8 * WN_H);
+  if (d.n_tiles == 0) return TTS_OK;
+  const bool f16 = d.compute == TTS_COMPUTE_F16;
+  static unsigned long long raised[2] = {0, 0};
+  const void* k = f16 ? reinterpret_cast<const void*>(wavenet_block_kernel<true>) : reinterpret_cast<const void*>(wavenet_block_kernel<false>);
+  if (raise_lds_limit(k, raised[f16 ? 1 : 0]) != hipSuccess) {
+    set_error("wavenet_block: raising the dynamic LDS limit failed");
+    return TTS_E_LAUNCH;
+  }
+  if (f16) hipLaunchKernelGGL((wavenet_block_kernel<true>), dim3(d.n_tiles), dim3(256), WB_LDS_BYTES, st, d);
+  else hipLaunchKernelGGL((wavenet_block_kernel<false>), dim3(d.n_tiles), dim3(256), WB_LDS_BYTES, st, d);
+  return launch_status("wavenet_block");
+}
 
 int wavenet_layer(const TtsWavenetDesc& d, hipStream_t st) { return wavenet_launch(d, nullptr, st); }
 

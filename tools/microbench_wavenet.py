@@ -1,4 +1,6 @@
-"""Micro-benchmark of tts_wavenet_layer vs the two-launch form at the bench shape (32 utterances x 320 squeezed frames)."""
+"""Micro-benchmark of tts_wavenet_layer vs the two-launch form at the bench shape (32 utterances x 320 squeezed frames).
+`--block [batch]`: the one-launch WaveNet block of the native PostFlow (wavenet_block: start conv + four layers) instead, timed by the
+stage profiler (HIP events around each of its 18 launches inside tts_postflow) beside the whole stage."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,7 +11,35 @@ from ims_toucan_prosody_variance_amd import capi, engine, packing
 from ims_toucan_prosody_variance_amd.ragged import Ragged
 
 
+def block(B):
+    """wavenet_block inside tts_postflow: B utterances of 128 phonemes x 5 frames (320 squeezed rows each), bf16, fixture weights."""
+    from ims_toucan_prosody_variance_amd import fixture_weights as fw, native, synthetic as syn
+    dev = torch.device("cuda:0")
+    pipe = native.NativePipeline(fw.acoustic_state_dict(), None, None, dev, precision="bf16")
+    L = 128
+    texts = [torch.from_numpy(syn.utterance_features(i, L, word_boundaries=False)).to(dev) for i in range(B)]
+    embs = torch.stack([torch.from_numpy(syn.utterance_embedding(i)) for i in range(B)]).to(dev)
+    durs = [torch.full((L,), 5, dtype=torch.int32, device=dev) for _ in range(B)]
+    zs = [torch.from_numpy(syn.postflow_noise(i, 5 * L)).to(dev) for i in range(B)]
+    packed = pipe.pack_inputs(texts, embs, [syn.LANG_EN] * B, durations=durs)
+    z_sq = pipe.squeeze_noise(zs, [5 * L] * B)
+    for _ in range(3):
+        pipe.forward(None, None, packed=packed, z_sq=z_sq)
+    torch.cuda.synchronize()
+    pipe.profile(1, "wavenet_block")
+    reps = 10
+    for _ in range(reps):
+        pipe.forward(None, None, packed=packed, z_sq=z_sq)
+    torch.cuda.synchronize()
+    s = pipe.profile_summary()["wavenet_block"]
+    pipe.profile(0)
+    print(f"rows {B * 320}: wavenet_block {s['avg_us']:.1f} us per launch over {s['launches']} launches "
+          f"({18 * s['avg_us'] / 1e3:.3f} ms per pass, {s['tflops']:.0f} TFLOP/s algorithmic)")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--block":
+        return block(int(sys.argv[2]) if len(sys.argv) > 2 else 32)
     dev = torch.device("cuda:0")
     ops = engine.Ops(dev)
     B, T, H = int(sys.argv[1]) if len(sys.argv) > 1 else 32, 320, 192
