@@ -265,6 +265,42 @@ def adjust_num_frames_centered(x, num_frames):
     return x[:num_frames]
 
 
+def batched_spectra(ops, logmel, waves):
+    """16 kHz waves -> (spectrum [rows, re | im] packed per utterance, Ragged of the frames inside it): the front end of
+    ``ProsodyExtractor`` (and of compare.SpeechComparator), one launch for the batch."""
+    dev = ops.device
+    bufs, begins, frames, off = [], [], [], 0
+    for w in waves:
+        x = np.asarray(w, dtype=np.float32).reshape(-1)
+        assert x.size > style.N_FFT // 2, "reference audio is too short for the centred STFT"
+        frames.append(1 + x.size // style.HOP)
+        x = np.pad(x, style.N_FFT // 2, mode="reflect")  # STFT(center=True, pad_mode="reflect")
+        rows = -(-x.size // style.HOP)
+        buf = np.zeros(rows * style.HOP, dtype=np.float32)
+        buf[: x.size] = x
+        bufs.append(buf)
+        begins.append(off)
+        off += rows
+    xd = torch.from_numpy(np.concatenate(bufs)).to(dev).view(off, style.HOP)
+    rows_rag = Ragged([len(b) // style.HOP for b in bufs], dev, begins=begins)
+    nb = logmel.bins
+    spec = ops.conv(logmel.dft, xd, ops.empty(off, 2 * nb), rows_rag, compute=capi.COMPUTE_F32, split_k=False)
+    return spec, Ragged(frames, dev, begins=begins)
+
+
+def batched_log_mel(ops, logmel, spec, rag):
+    """The spectrum of ``batched_spectra`` -> log-mel [rows, 80] in the same rows."""
+    nb = logmel.bins
+    rows = rag.total_rows
+    mag = ops.empty(rows, nb)
+    capi.check(ops.lib.tts_complex_magnitude(spec.data_ptr(), 2 * nb, mag.data_ptr(), nb, rows, nb, ops.stream()), "tts_complex_magnitude")
+    melp = ops.conv(logmel.mel, mag, ops.empty(rows, style.N_MELS), rag, compute=capi.COMPUTE_F32, split_k=False)
+    out = ops.empty(rows, style.N_MELS)
+    capi.check(ops.lib.tts_log10_floor(melp.data_ptr(), style.N_MELS, out.data_ptr(), style.N_MELS, rows, style.N_MELS, 1e-10, ops.stream()),
+               "tts_log10_floor")
+    return out
+
+
 class ProsodyExtractor:
     """extract_prosody (UtteranceCloner.py:46-145) for ragged batches: one aligner, one log-mel front end."""
 
@@ -294,35 +330,10 @@ class ProsodyExtractor:
 
     def spectra(self, waves):
         """16 kHz waves -> (spectrum [rows, re | im] packed per utterance, Ragged of the frames inside it)."""
-        ops, dev = self.ops, self.device
-        bufs, begins, frames, off = [], [], [], 0
-        for w in waves:
-            x = np.asarray(w, dtype=np.float32).reshape(-1)
-            assert x.size > style.N_FFT // 2, "reference audio is too short for the centred STFT"
-            frames.append(1 + x.size // style.HOP)
-            x = np.pad(x, style.N_FFT // 2, mode="reflect")  # STFT(center=True, pad_mode="reflect")
-            rows = -(-x.size // style.HOP)
-            buf = np.zeros(rows * style.HOP, dtype=np.float32)
-            buf[: x.size] = x
-            bufs.append(buf)
-            begins.append(off)
-            off += rows
-        xd = torch.from_numpy(np.concatenate(bufs)).to(dev).view(off, style.HOP)
-        rows_rag = Ragged([len(b) // style.HOP for b in bufs], dev, begins=begins)
-        nb = self.logmel.bins
-        spec = ops.conv(self.logmel.dft, xd, ops.empty(off, 2 * nb), rows_rag, compute=capi.COMPUTE_F32, split_k=False)
-        return spec, Ragged(frames, dev, begins=begins)
+        return batched_spectra(self.ops, self.logmel, waves)
 
     def log_mel(self, spec, rag):
-        ops, nb = self.ops, self.logmel.bins
-        rows = rag.total_rows
-        mag = ops.empty(rows, nb)
-        capi.check(ops.lib.tts_complex_magnitude(spec.data_ptr(), 2 * nb, mag.data_ptr(), nb, rows, nb, ops.stream()), "tts_complex_magnitude")
-        melp = ops.conv(self.logmel.mel, mag, ops.empty(rows, style.N_MELS), rag, compute=capi.COMPUTE_F32, split_k=False)
-        out = ops.empty(rows, style.N_MELS)
-        capi.check(ops.lib.tts_log10_floor(melp.data_ptr(), style.N_MELS, out.data_ptr(), style.N_MELS, rows, style.N_MELS, 1e-10, ops.stream()),
-                   "tts_log10_floor")
-        return out
+        return batched_log_mel(self.ops, self.logmel, spec, rag)
 
     def token_average(self, frame_values, rag, durations, keep, full_begin, n_full, mode):
         ops, dev = self.ops, self.device

@@ -257,6 +257,24 @@ CURVE_PROTOTYPES = {
 }
 PROSODY_CURVE_COLUMNS = 5  # include/toucan_prosody_curves.h TTS_PROSODY_CURVE_COLUMNS
 
+
+
+class TtsDtwPair(C.Structure):
+    _fields_ = [("begin_a", _i), ("frames_a", _i), ("begin_b", _i), ("frames_b", _i), ("scratch_off", _l), ("path_begin", _l)]
+
+
+# symbol -> (restype, argtypes); mirrors include/toucan_compare.h (cepstra, DTW and the sums along its path: csrc/compare.hip) one to one
+COMPARE_PROTOTYPES = {
+    "tts_dtw_max_frames": (C.c_int, []),
+    "tts_mel_cepstra": (C.c_int, [_p, _i, _i, _p, _i, _p, _i, _p, _p]),
+    "tts_dtw": (C.c_int, [_p, _i, _p, _i, _i, C.POINTER(TtsDtwPair), _p, _i, _p, _l, _i, _p, _l, _p, _p, _p]),
+    "tts_dtw_path_sums": (C.c_int, [_p, _i, _p, _i, _i, C.POINTER(TtsDtwPair), _p, _i, _p, _l, _p, _p, _p, _p, _p]),
+}
+COMPARE_MELS, COMPARE_MAX_CEP = 80, 32  # include/toucan_compare.h TTS_COMPARE_MELS, TTS_COMPARE_MAX_CEP
+DTW_MAX_FRAMES, DTW_LDS_BP_BYTES, DTW_N_SUMS = 4096, 40960, 12  # TTS_DTW_MAX_FRAMES, TTS_DTW_LDS_BP_BYTES, TTS_DTW_N_SUMS
+# the columns of tts_dtw_path_sums, in the order of the header's TTS_DTW_SUM_* indices
+DTW_SUM_COLUMNS = ("mcd", "diag", "vv", "sq_hz", "sq_cents", "x", "y", "xx", "yy", "xy", "gross", "vuv")
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -281,7 +299,7 @@ def lib():
     _assert_single_hip_runtime()
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
-            list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()):
+            list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -72,8 +72,11 @@ class UtteranceCloner:
                                           dropout_masks=None if dropout_masks is None else [dropout_masks])[0]
 
     def clone_utterance(self, path_to_reference_audio_for_intonation, path_to_reference_audio_for_voice, transcription_of_intonation_reference,
-                        filename_of_result=None, lang="de", f0=None, speech_bounds=None, z_noise=None):
-        """UtteranceCloner.py:147-164: the voice of one recording speaking with the prosody of another."""
+                        filename_of_result=None, lang="de", f0=None, speech_bounds=None, z_noise=None, evaluate=False):
+        """UtteranceCloner.py:147-164: the voice of one recording speaking with the prosody of another.  evaluate (additive): also
+        return how close the clone is to the intonation reference - (waveform, dict) with the measures of
+        compare.SpeechComparator.compare (MCD along the warping path, F0 RMSE, log-F0 correlation, GPE, VDE, FFE): the 24 kHz clone
+        without its padded silences against the speech span of the normalised 16 kHz reference, the wave the prosody was taken from."""
         self.tts.set_utterance_embedding(path_to_reference_audio=path_to_reference_audio_for_voice)
         duration, pitch, energy, sil_start, sil_end = self.extract_prosody(transcription_of_intonation_reference,
                                                                            path_to_reference_audio_for_intonation, lang=lang, f0=f0,
@@ -81,7 +84,15 @@ class UtteranceCloner:
         self.tts.set_language(lang)
         cloned = self.tts(transcription_of_intonation_reference, view=False, durations=duration, pitch=pitch, energy=energy,
                           input_is_phones=True, z_noise=z_noise)
-        return self._pad_and_write(cloned, sil_start, sil_end, filename_of_result)
+        utt = self._pad_and_write(cloned, sil_start, sil_end, filename_of_result)
+        if not evaluate:
+            return utt
+        data, sr = style.read_audio(path_to_reference_audio_for_intonation)
+        ref16 = style.normalize_reference_audio(data, sr)
+        if speech_bounds is not None:
+            ref16 = ref16[int(speech_bounds[0]):int(speech_bounds[1])]
+        report = self.tts._comparator().compare([cloned.reshape(-1).float().cpu().numpy()], [ref16], self.tts.SAMPLE_RATE, style.SR)[0]
+        return utt, report
 
     def biblical_accurate_angel_mode(self, path_to_reference_audio_for_intonation, transcription_of_intonation_reference,
                                      list_of_speaker_references_for_ensemble, filename_of_result=None, lang="de", f0=None, speech_bounds=None,

@@ -11,7 +11,9 @@ script written against the reference (run_text_to_file_reader.py:8-16) works unc
   strings skipped, 24 kHz output or sample-doubled 48 kHz PCM16), ``read_aloud`` (:287-309), the language / embedding setters
 * additive API: ``synthesize_batch`` (ragged batches, optionally sharded over the ranks of torch.distributed; every prosody scale
   a scalar or one value per utterance), ``synthesize_grid`` (one text over a grid of prosody scales, with the statistics of what
-  each scale did), ``prosody_curves=`` / ``curves=`` (per-phoneme prosody curves: stress one word, prosody.emphasis)
+  each scale did), ``prosody_curves=`` / ``curves=`` (per-phoneme prosody curves: stress one word, prosody.emphasis),
+  ``evaluate_against_recordings`` (synthesise and measure against recordings of the same sentences: MCD along a DTW path and
+  the F0 errors, compare.py)
 
 * ``set_utterance_embedding(path)`` (:103-114): reference audio -> log-mel -> GST style embedding on the GPU (style.py)
 
@@ -351,6 +353,41 @@ class ToucanTTSInterface(torch.nn.Module):
                                         energy=energy, sample_rate=sample_rate, pcm16=pcm16, **kw)
         from . import distributed as dd
         return dd.synthesize_sharded(self, feats, embs, z_noise, durations, pitch, energy, kw)
+
+    def _comparator(self):
+        if getattr(self, "_comparator_obj", None) is None:
+            from . import compare
+            self._comparator_obj = compare.SpeechComparator(self.device)
+        return self._comparator_obj
+
+    def evaluate_against_recordings(self, texts, recordings, input_is_phones=True, keep_waves=False, f0="track", **synthesis_keywords):
+        """Additive API: synthesise ``texts`` as one batch (``synthesize_batch`` with ``synthesis_keywords``: prosody scales, curves,
+        gold prosody, ``z_noise``, ``utterance_embeddings``) and measure how close each waveform is to a recording of the same
+        sentence (compare.SpeechComparator.compare): mel-cepstral distortion along the warping path, F0 RMSE in
+        Hz and cents, log-F0 correlation, GPE, VDE and FFE, the recording being the reference side.  recordings: per text a path
+        (style.read_audio) or a (wave, sample rate) tuple; several channels are averaged.  f0: as ``compare`` takes it.  -> one dict
+        per text; with ``keep_waves`` it also holds "synth" (float32, 24 kHz), "recording" (mono, float32) and "recording_sr", the two
+        waves that were compared.  ValueError for lists of unequal length, for ``distributed=True`` and for ``sample_rate`` /
+        ``pcm16`` (the comparison takes the 24 kHz float waveform), and what ``compare`` refuses."""
+        if synthesis_keywords.get("distributed"):
+            raise ValueError("evaluate_against_recordings is not available with distributed=True: the comparison runs on one device")
+        if synthesis_keywords.get("sample_rate") is not None or synthesis_keywords.get("pcm16"):
+            raise ValueError("evaluate_against_recordings compares the 24 kHz float waveform: sample_rate / pcm16 do not apply")
+        if len(texts) != len(recordings):
+            raise ValueError(f"{len(texts)} texts for {len(recordings)} recordings")
+        from . import style
+        recs, srs = [], []
+        for r in recordings:
+            data, sr = style.read_audio(r) if isinstance(r, (str, os.PathLike)) else r
+            data = np.asarray(data, dtype=np.float32)
+            recs.append(data.mean(axis=1) if data.ndim == 2 else data.reshape(-1))
+            srs.append(int(sr))
+        synth = [w.float().cpu().numpy() for w in self.synthesize_batch(texts, input_is_phones=input_is_phones, **synthesis_keywords)]
+        results = self._comparator().compare(synth, recs, self.SAMPLE_RATE, srs, f0=f0)
+        if keep_waves:
+            for r, s, w, sr in zip(results, synth, recs, srs):
+                r.update(synth=s, recording=w, recording_sr=sr)
+        return results
 
     def synthesize_ensemble(self, text, utterance_embeddings, durations=None, pitch=None, energy=None, input_is_phones=True, z_noise=None,
                             sample_rate=None, pcm16=False):

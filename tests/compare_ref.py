@@ -1,0 +1,174 @@
+"""Float64 restatement of the comparison of two renditions (ims-toucan-prosody-variance_amd/compare.py,
+csrc/compare.hip): the cepstra, dynamic time warping vectorised by anti-diagonals (with, for every cell, how close its decision
+was), the sums along a path, and the seeded cases the CPU and GPU tests share."""
+import functools
+import math
+
+import numpy as np
+
+N_MELS, N_CEP = 80, 13
+SUM_COLUMNS = ("mcd", "diag", "vv", "sq_hz", "sq_cents", "x", "y", "xx", "yy", "xy", "gross", "vuv")
+CASE_SIZES = ((1, 1), (1, 7), (5, 3), (64, 64), (65, 130), (257, 190), (300, 420), (4096, 64))
+MIN_GAP = 1e-10  # every decision of every case is wider than this (relative): eight orders above fp64 rounding
+
+
+def dct_table(n_cep=N_CEP):
+    k = np.arange(1, n_cep + 1, dtype=np.float64)[:, None]
+    m = np.arange(N_MELS, dtype=np.float64)[None, :]
+    return math.sqrt(2.0 / N_MELS) * math.log(10.0) * np.cos(np.pi * k * (m + 0.5) / N_MELS)
+
+
+def cepstra(logmel, n_cep=N_CEP):
+    """Log-mel [T, 80] float32 -> cepstra [T, n_cep] float32, correctly rounded: every table entry is split into two halves of at
+    most 26 bits (Veltkamp), so that both products with a 24-bit log-mel value are exact in float64; math.fsum adds the 160 exact
+    terms of a coefficient without error, and its float64 result is rounded once more to float32."""
+    tab = dct_table(n_cep)
+    c = tab * 134217729.0  # 2^27 + 1
+    hi = c - (c - tab)
+    lo = tab - hi
+    x = np.asarray(logmel, dtype=np.float32).astype(np.float64)
+    assert x.ndim == 2 and x.shape[1] == N_MELS
+    terms = np.concatenate([x[:, None, :] * hi[None, :, :], x[:, None, :] * lo[None, :, :]], axis=2)  # [T, n_cep, 160], each exact
+    return np.asarray([[math.fsum(row) for row in frame] for frame in terms], dtype=np.float64).reshape(len(x), n_cep).astype(np.float32)
+
+
+def squared_distance(a, b):
+    """[Ta, Tb] float64: sum_k (a[i, k] - b[j, k])^2, k in index order."""
+    a, b = np.asarray(a, dtype=np.float32).astype(np.float64), np.asarray(b, dtype=np.float32).astype(np.float64)
+    acc = np.zeros((len(a), len(b)))
+    for k in range(a.shape[1]):
+        df = a[:, None, k] - b[None, :, k]
+        acc += df * df
+    return acc
+
+
+def backtrack(code):
+    """Back-pointers [Ta, Tb] (0 diagonal, 1 up, 2 left) -> the path [P, 2] int32 from (0, 0) to (Ta - 1, Tb - 1)."""
+    i, j = code.shape[0] - 1, code.shape[1] - 1
+    pts = [(i, j)]
+    while i or j:
+        c = code[i, j]
+        i, j = (i - 1, j - 1) if c == 0 else (i - 1, j) if c == 1 else (i, j - 1)
+        pts.append((i, j))
+    return np.asarray(pts[::-1], dtype=np.int32)
+
+
+def dtw(a, b):
+    """-> {"cost": D(Ta-1, Tb-1), "path": [P, 2] int32, "gap": the smallest relative gap between the best and the second-best
+    predecessor over the cells with at least two finite ones (inf when there is no such cell), "D": [Ta, Tb]}.  One anti-diagonal at
+    a time; the predecessor is taken with strict < in the order diagonal, up, left."""
+    d = np.sqrt(squared_distance(a, b))
+    Ta, Tb = d.shape
+    D = np.full((Ta + 1, Tb + 1), np.inf)  # D[i + 1, j + 1] = D(i, j); the border stands for the missing neighbours
+    D[0, 0] = 0.0  # so that D(0, 0) = d(0, 0) + 0
+    code = np.zeros((Ta, Tb), dtype=np.uint8)
+    gap = np.inf
+    for s in range(Ta + Tb - 1):
+        i = np.arange(max(0, s - Tb + 1), min(Ta - 1, s) + 1)
+        j = s - i
+        diag, up, left = D[i, j], D[i, j + 1], D[i + 1, j]
+        best, c = diag.copy(), np.zeros(len(i), dtype=np.uint8)
+        m = up < best
+        best[m], c[m] = up[m], 1
+        m = left < best
+        best[m], c[m] = left[m], 2
+        D[i + 1, j + 1] = d[i, j] + best
+        code[i, j] = c
+        three = np.sort(np.stack([diag, up, left]), axis=0)
+        two = np.isfinite(three[1])
+        if two.any():
+            first, second = three[0][two], three[1][two]
+            rel = np.where(second > 0, (second - first) / np.where(second > 0, second, 1.0), 0.0)
+            gap = min(gap, float(rel.min()))
+    return {"cost": float(D[Ta, Tb]), "path": backtrack(code), "gap": gap, "D": D[1:, 1:]}
+
+
+def dtw_naive(a, b):
+    """The same by a plain double loop -> (cost, path)."""
+    d = np.sqrt(squared_distance(a, b))
+    Ta, Tb = d.shape
+    D = np.full((Ta, Tb), np.inf)
+    code = np.zeros((Ta, Tb), dtype=np.uint8)
+    for i in range(Ta):
+        for j in range(Tb):
+            if i == 0 and j == 0:
+                D[0, 0] = d[0, 0]
+                continue
+            best, c = (D[i - 1, j - 1] if i and j else np.inf), 0
+            if i and D[i - 1, j] < best:
+                best, c = D[i - 1, j], 1
+            if j and D[i, j - 1] < best:
+                best, c = D[i, j - 1], 2
+            D[i, j], code[i, j] = d[i, j] + best, c
+    return float(D[-1, -1]), backtrack(code)
+
+
+def path_sums(a, b, path, f0_a=None, f0_b=None):
+    """float64 [12] (columns SUM_COLUMNS) along `path`; every sum is exact (math.fsum) over float64 terms."""
+    path = np.asarray(path).reshape(-1, 2)
+    i, j = path[:, 0], path[:, 1]
+    a64, b64 = np.asarray(a, dtype=np.float32).astype(np.float64)[i], np.asarray(b, dtype=np.float32).astype(np.float64)[j]
+    d2 = np.zeros(len(path))
+    for k in range(a64.shape[1]):
+        df = a64[:, k] - b64[:, k]
+        d2 += df * df
+    out = dict.fromkeys(SUM_COLUMNS, 0.0)
+    out["mcd"] = math.fsum(np.sqrt(2.0 * d2))
+    step = np.diff(path, axis=0)
+    out["diag"] = float(((step[:, 0] == 1) & (step[:, 1] == 1)).sum())
+    if f0_a is not None:
+        fa = np.asarray(f0_a, dtype=np.float32).astype(np.float64)[i]
+        fb = np.asarray(f0_b, dtype=np.float32).astype(np.float64)[j]
+        vv = (fa > 0) & (fb > 0)
+        fa_v, fb_v = fa[vv], fb[vv]
+        x, y = np.log(fa_v), np.log(fb_v)
+        cents = 1200.0 * np.log2(fa_v / fb_v)
+        out.update(vv=float(vv.sum()), sq_hz=math.fsum((fa_v - fb_v) ** 2), sq_cents=math.fsum(cents * cents), x=math.fsum(x), y=math.fsum(y),
+                   xx=math.fsum(x * x), yy=math.fsum(y * y), xy=math.fsum(x * y),
+                   gross=float((np.abs(fa_v - fb_v) > 0.2 * fb_v).sum()), vuv=float(((fa > 0) != (fb > 0)).sum()))
+    return np.asarray([out[c] for c in SUM_COLUMNS])
+
+
+# ---- seeded cases ------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def cases():
+    """[(a [Ta, 13], b [Tb, 13])] float32 for CASE_SIZES, from one generator consumed in case order: b is a warped, noisy a."""
+    rng = np.random.default_rng(0)
+    out = []
+    for Ta, Tb in CASE_SIZES:
+        a = rng.standard_normal((Ta, N_CEP)).astype(np.float32)
+        idx = np.round(np.linspace(0, Ta - 1, Tb)).astype(np.int64)
+        b = (a[idx] + 0.3 * rng.standard_normal((Tb, N_CEP))).astype(np.float32)
+        a.setflags(write=False)
+        b.setflags(write=False)
+        out.append((a, b))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def solved(n):
+    """The restatement of case n, computed once per process and shared (read-only) by the tests."""
+    a, b = cases()[n]
+    out = dtw(a, b)
+    del out["D"]
+    out["path"].setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def f0_tracks(n):
+    """(f0 of side a [Ta], of side b [Tb]) float32 for case n: a slow contour around 150 Hz on side b, side a following it through
+    the case's own warp with 3 % noise and every ninth frame half an octave off (a gross error); voiceless stretches (0) on both
+    sides, overlapping in part."""
+    Ta, Tb = CASE_SIZES[n]
+    rng = np.random.default_rng(100 + n)
+    fb = 150.0 + 40.0 * np.sin(np.arange(Tb) / 9.0) + rng.normal(0, 2.0, Tb)
+    idx = np.round(np.linspace(0, Tb - 1, Ta)).astype(np.int64)
+    fa = fb[idx] * (1.0 + 0.03 * rng.standard_normal(Ta))
+    fa[::9] *= 2.0 ** 0.5
+    for f, T, lo, hi in ((fa, Ta, 0.30, 0.45), (fb, Tb, 0.40, 0.55), (fa, Ta, 0.80, 0.85)):
+        f[int(lo * T):int(hi * T)] = 0.0
+    fa, fb = fa.astype(np.float32), fb.astype(np.float32)
+    fa.setflags(write=False)
+    fb.setflags(write=False)
+    return fa, fb
