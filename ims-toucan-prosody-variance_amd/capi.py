@@ -275,6 +275,16 @@ DTW_MAX_FRAMES, DTW_LDS_BP_BYTES, DTW_N_SUMS = 4096, 40960, 12  # TTS_DTW_MAX_FR
 # the columns of tts_dtw_path_sums, in the order of the header's TTS_DTW_SUM_* indices
 DTW_SUM_COLUMNS = ("mcd", "diag", "vv", "sq_hz", "sq_cents", "x", "y", "xx", "yy", "xy", "gross", "vuv")
 
+# symbol -> (restype, argtypes); mirrors include/toucan_loudness.h (BS.1770 loudness and the gain to a target: csrc/loudness.hip) one to one
+LOUDNESS_PROTOTYPES = {
+    "tts_loudness_tile_segments": (C.c_int, []),
+    "tts_kweight_energy": (C.c_int, [_p, _l, _p, _p, _i, _i, _p, _l, _p, _p, _p, _p]),
+    "tts_loudness_gate": (C.c_int, [_p, _p, _l, _p, _i, _i, _l, C.c_double, C.c_double, _p, _p]),
+    "tts_apply_gain": (C.c_int, [_p, _l, _p, _p, _i, _l, _p, _p, _p]),
+}
+# include/toucan_loudness.h TTS_LOUDNESS_MIN_RATE, _MAX_RATE, _COLUMNS, _TABLE_DOUBLES
+LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE, LOUDNESS_N_COLUMNS, LOUDNESS_TABLE_DOUBLES = 8000, 192000, 8, 24
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -299,7 +309,8 @@ def lib():
     _assert_single_hip_runtime()
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
-            list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()):
+            list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()) + \
+            list(LOUDNESS_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -13,7 +13,8 @@ script written against the reference (run_text_to_file_reader.py:8-16) works unc
   a scalar or one value per utterance), ``synthesize_grid`` (one text over a grid of prosody scales, with the statistics of what
   each scale did), ``prosody_curves=`` / ``curves=`` (per-phoneme prosody curves: stress one word, prosody.emphasis),
   ``evaluate_against_recordings`` (synthesise and measure against recordings of the same sentences: MCD along a DTW path and
-  the F0 errors, compare.py)
+  the F0 errors, compare.py), ``loudness=`` / ``peak_ceiling=`` (every utterance brought to a target integrated loudness after
+  ITU-R BS.1770 under a sample-peak ceiling, on the device: loudness.py)
 
 * ``set_utterance_embedding(path)`` (:103-114): reference audio -> log-mel -> GST style embedding on the GPU (style.py)
 
@@ -162,6 +163,7 @@ class ToucanTTSInterface(torch.nn.Module):
         self._style = None
         self.last_prosody_stats = None  # (before, after) of the last batch that took per-utterance prosody scales or curves
         self.last_prosody_span_stats = None  # per utterance (before, after) of its Spans, of the last batch that took prosody curves
+        self.last_loudness = None  # float64 [B, 8] on the device (loudness.LOUDNESS_COLUMNS) of the last call that took loudness=
 
 
         self.default_utterance_embedding = checkpoint["default_emb"].to(self.device)
@@ -214,14 +216,18 @@ class ToucanTTSInterface(torch.nn.Module):
                 z_noise=None,
                 sample_rate=None,
                 pcm16=False,
-                prosody_curves=None):
+                prosody_curves=None,
+                loudness=None,
+                peak_ceiling=-1.0):
         """The reference's signature (ToucanTTSInterface.py:132-143) plus additive keywords.  ``z_noise`` [80, T]: the PostFlow
         noise 0.8 N(0,1) the reference draws inside the model (Glow.py:363), so that a call can be reproduced and checked
         against the oracle; None draws it on the device.  ``sample_rate`` / ``pcm16``: the waveform at another rate than 24 kHz
         and / or as int16, converted on the device (resample.py); the figure of ``view`` keeps drawing the 24 kHz wave.
         ``prosody_curves``: this utterance's per-phoneme curves, an [L, 5] array or a list of ``prosody.Span`` (as one entry of
-        ``synthesize_batch``'s keyword, documented there); None is the call as it was."""
+        ``synthesize_batch``'s keyword, documented there); None is the call as it was.  ``loudness`` / ``peak_ceiling``: as in
+        ``synthesize_batch``; the figure of ``view`` then draws the normalised 24 kHz wave."""
         self._check_output_format(sample_rate, pcm16)
+        self._check_loudness(loudness, peak_ceiling)
         with torch.inference_mode():
             phones = self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
             curves = {} if prosody_curves is None else dict(prosody_curves=[prosody_curves])
@@ -233,6 +239,7 @@ class ToucanTTSInterface(torch.nn.Module):
                                                    duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
                                                    energy_variance_scale=energy_variance_scale,
                                                    pause_duration_scaling_factor=pause_duration_scaling_factor, **curves)
+            wav24 = self._normalize(wav24, spans, loudness, peak_ceiling)
             wav, out_spans = self._convert(wav24, spans, sample_rate, pcm16)
             wavs = [wav[b:b + n] for b, n in out_spans]
         if view or return_plot_as_filepath:  # ToucanTTSInterface.py:171-226 (matplotlib only: plotting.py)
@@ -268,8 +275,9 @@ class ToucanTTSInterface(torch.nn.Module):
         self.last_prosody_span_stats = out.get("prosody_span_stats")
         return wav, list(zip(rag.begins, rag.lengths))
 
-    def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, **kw):
+    def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, **kw):
         wav, spans = self._synthesize_packed(phones, embs, langs, z_noise=z_noise, **kw)
+        wav = self._normalize(wav, spans, loudness, peak_ceiling)
         wav, spans = self._convert(wav, spans, sample_rate, pcm16)
         return [wav[b:b + n] for b, n in spans]
 
@@ -297,6 +305,31 @@ class ToucanTTSInterface(torch.nn.Module):
             return wav, spans
         return self._resampler().resample(wav.contiguous(), spans, self.SAMPLE_RATE, sample_rate or self.SAMPLE_RATE, pcm16)
 
+    @staticmethod
+    def _check_loudness(loudness, peak_ceiling):
+        """ValueError for a target or a ceiling that is not finite, or a ceiling above 0 dBFS; True if the waveform is to be
+        normalised at all (``loudness`` is not None)."""
+        if loudness is None:
+            return False
+        from . import loudness as ld
+        ld.check_target(loudness, peak_ceiling)
+        return True
+
+    def _meter(self):
+        if getattr(self, "_meter_obj", None) is None:
+            from . import loudness as ld
+            self._meter_obj = ld.LoudnessMeter(self.device)
+        return self._meter_obj
+
+    def _normalize(self, wav, spans, loudness, peak_ceiling):
+        """The packed 24 kHz waveform with every utterance at ``loudness`` LUFS (ITU-R BS.1770 integrated loudness) or as close
+        as the sample-peak ceiling ``peak_ceiling`` dBFS allows, measured and scaled on the device behind the vocoder on its
+        stream; ``self.last_loudness`` gets the statistics.  None returns the waveform as it came, without a launch."""
+        if not self._check_loudness(loudness, peak_ceiling):
+            return wav
+        wav, self.last_loudness = self._meter().normalize(wav.contiguous(), spans, self.SAMPLE_RATE, loudness, peak_ceiling)
+        return wav
+
     def predict_frame_counts(self, feats, embs, pitch=None, energy=None, **kw):
         """Mel frames each utterance will get (stage A only) - the balancing key of the multi-GPU deal."""
         emb = torch.stack([e.reshape(-1).to(torch.float32).cpu() for e in embs])
@@ -305,7 +338,8 @@ class ToucanTTSInterface(torch.nn.Module):
 
     def synthesize_batch(self, texts, input_is_phones=True, utterance_embeddings=None, z_noise=None, durations=None, pitch=None,
                          energy=None, duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
-                         pause_duration_scaling_factor=1.0, distributed=False, sample_rate=None, pcm16=False, prosody_curves=None):
+                         pause_duration_scaling_factor=1.0, distributed=False, sample_rate=None, pcm16=False, prosody_curves=None,
+                         loudness=None, peak_ceiling=-1.0):
         """Additive API: a ragged batch in one pass; each utterance equals the reference run on it alone (16-bit configurations: bit
         for bit whatever the batch; fp32: durations / pitch / energy bit for bit, the mel to fp32 rounding order - DESIGN.md section 4).
         texts: phoneme strings (or [L,62] feature tensors).  durations / pitch / energy: optional per-utterance gold prosody (the
@@ -330,7 +364,18 @@ class ToucanTTSInterface(torch.nn.Module):
         Spans in list order (empty for arrays); column 6 of a Span's block is the frames it occupies after the curves, which with the
         frames in front of it (``self.last_durations``) tells which samples carry the emphasised word.  ValueError for a wrong
         shape, a Span outside its utterance, a value that is not finite or a duration factor that is not positive (the message
-        names the utterance and the phoneme), and for curves with ``distributed=True``."""
+        names the utterance and the phoneme), and for curves with ``distributed=True``.
+        ``loudness``: None (the call as it was: no launch, the same bits) or a target in LUFS, e.g. -23 (EBU R 128).  Every
+        utterance's integrated loudness after ITU-R BS.1770-4 (K-weighting, 400 ms blocks, absolute gate at -70 LUFS, relative gate
+        at -10 LU) is measured at 24 kHz on the device and the utterance scaled by one gain to the target, before the conversion of
+        ``sample_rate`` / ``pcm16``; ``peak_ceiling`` (dBFS, at most 0) limits the gain so that no SAMPLE exceeds it - a sample peak,
+        not an oversampled true peak.  An utterance without a loudness (shorter than 400 ms, or silent) keeps its bits.
+        ``self.last_loudness``: float64 [B, 8] on the device, columns ``loudness.LOUDNESS_COLUMNS`` (the loudness found, the peak,
+        the blocks and what each gate kept, the loudest block, the gain applied, the loudness reached).  ValueError for a target or
+        ceiling that is not finite, a ceiling above 0, and with ``distributed=True``."""
+        if distributed and loudness is not None:
+            raise ValueError("loudness is not available with distributed=True: the sharded exchange carries the waveforms as synthesised")
+        self._check_loudness(loudness, peak_ceiling)
         if distributed and (sample_rate is not None or pcm16):
             raise ValueError("sample_rate / pcm16 are not available with distributed=True: the sharded exchange carries 24 kHz float32")
         self._check_output_format(sample_rate, pcm16)
@@ -350,7 +395,7 @@ class ToucanTTSInterface(torch.nn.Module):
                 kw["prosody_curves"] = prosody_curves
             with torch.inference_mode():
                 return self._synthesize(feats, embs, [self._lang()] * len(feats), z_noise=z_noise, durations=durations, pitch=pitch,
-                                        energy=energy, sample_rate=sample_rate, pcm16=pcm16, **kw)
+                                        energy=energy, sample_rate=sample_rate, pcm16=pcm16, loudness=loudness, peak_ceiling=peak_ceiling, **kw)
         from . import distributed as dd
         return dd.synthesize_sharded(self, feats, embs, z_noise, durations, pitch, energy, kw)
 
@@ -368,11 +413,14 @@ class ToucanTTSInterface(torch.nn.Module):
         (style.read_audio) or a (wave, sample rate) tuple; several channels are averaged.  f0: as ``compare`` takes it.  -> one dict
         per text; with ``keep_waves`` it also holds "synth" (float32, 24 kHz), "recording" (mono, float32) and "recording_sr", the two
         waves that were compared.  ValueError for lists of unequal length, for ``distributed=True`` and for ``sample_rate`` /
-        ``pcm16`` (the comparison takes the 24 kHz float waveform), and what ``compare`` refuses."""
+        ``pcm16`` (the comparison takes the 24 kHz float waveform), for ``loudness`` (both waves are divided by their peaks anyway), and
+        what ``compare`` refuses."""
         if synthesis_keywords.get("distributed"):
             raise ValueError("evaluate_against_recordings is not available with distributed=True: the comparison runs on one device")
         if synthesis_keywords.get("sample_rate") is not None or synthesis_keywords.get("pcm16"):
             raise ValueError("evaluate_against_recordings compares the 24 kHz float waveform: sample_rate / pcm16 do not apply")
+        if synthesis_keywords.get("loudness") is not None:
+            raise ValueError("evaluate_against_recordings divides both waves by their peaks before it compares them: loudness does not apply")
         if len(texts) != len(recordings):
             raise ValueError(f"{len(texts)} texts for {len(recordings)} recordings")
         from . import style
@@ -390,17 +438,21 @@ class ToucanTTSInterface(torch.nn.Module):
         return results
 
     def synthesize_ensemble(self, text, utterance_embeddings, durations=None, pitch=None, energy=None, input_is_phones=True, z_noise=None,
-                            sample_rate=None, pcm16=False):
+                            sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0):
         """Several voices speaking one text with the same prosody, averaged (UtteranceCloner.py:166-194's ensemble) - as ONE batch
         over the voices instead of a loop that swaps the default embedding.  Without gold durations the voices may predict
-        different lengths; the mean is then taken over the common prefix.  ``sample_rate`` / ``pcm16`` convert the 24 kHz mean."""
+        different lengths; the mean is then taken over the common prefix.  ``sample_rate`` / ``pcm16`` convert the 24 kHz mean;
+        ``loudness`` / ``peak_ceiling`` (as in ``synthesize_batch``) normalise the mean, before that conversion."""
         convert = self._check_output_format(sample_rate, pcm16)
+        self._check_loudness(loudness, peak_ceiling)
         n = len(utterance_embeddings)
         rep = lambda v: None if v is None else [v] * n
         waves = self.synthesize_batch([text] * n, input_is_phones=input_is_phones, utterance_embeddings=list(utterance_embeddings),
                                       durations=rep(durations), pitch=rep(pitch), energy=rep(energy), z_noise=z_noise)
         m = min(w.numel() for w in waves)
         mean = torch.stack([w[:m] for w in waves]).mean(dim=0)
+        with torch.inference_mode():
+            mean = self._normalize(mean, [(0, m)], loudness, peak_ceiling)
         if not convert:
             return mean
         wav, spans = self._convert(mean, [(0, m)], sample_rate, pcm16)
@@ -408,7 +460,7 @@ class ToucanTTSInterface(torch.nn.Module):
 
     def synthesize_grid(self, text, duration_scaling_factors=(1.0,), pitch_variance_scales=(1.0,), energy_variance_scales=(1.0,),
                         pause_duration_scaling_factors=(1.0,), input_is_phones=True, utterance_embedding=None, durations=None, pitch=None,
-                        energy=None, z_noise=None, sample_rate=None, pcm16=False, curves=None):
+                        energy=None, z_noise=None, sample_rate=None, pcm16=False, curves=None, loudness=None, peak_ceiling=-1.0):
         """Additive API: ONE text (a phoneme string, or its [L, 62] feature tensor) at every combination of the four tuples of prosody scales - the Cartesian product in row-major
         order of the tuples as listed (the pause factor varies fastest) - synthesised as ragged batches of at most MAX_FILE_BATCH
         variants with per-utterance scales instead of one pass per setting.  Returns one dict per variant, in that order:
@@ -423,8 +475,12 @@ class ToucanTTSInterface(torch.nn.Module):
         all scale variants under curves[0], then under curves[1], ...  The dicts then also hold ``curve`` (the index into
         ``curves``) and ``span_stats`` = (before [n, 8], after [n, 8]) of that alternative's Spans; column 6 of a Span's block is the
         frames it occupies.  ``curves=[prosody.emphasis(feats, [k]) for k in range(len(prosody.word_spans(feats)))]`` is the emphasis
-        sweep over the words of a sentence in one call."""
+        sweep over the words of a sentence in one call.
+        ``loudness`` / ``peak_ceiling`` (as in ``synthesize_batch``): every variant is normalised on its own and its dict gains
+        ``loudness``, its float64 [8] row of statistics on the device; ``self.last_loudness`` holds all rows, in variant order."""
         self._check_output_format(sample_rate, pcm16)
+        normalise = self._check_loudness(loudness, peak_ceiling)
+        rows = []
         variants = prosody.grid(duration_scaling_factors, pitch_variance_scales, energy_variance_scales, pause_duration_scaling_factors)
         which = [None] * len(variants)  # the curve alternative of every variant
         if curves is not None:
@@ -451,22 +507,33 @@ class ToucanTTSInterface(torch.nn.Module):
                                                          durations=rep(durations), pitch=rep(pitch), energy=rep(energy),
                                                          **{name: [v[k] for v in chunk] for k, name in enumerate(prosody.KNOBS)}, **kw)
                 before, after = self.last_prosody_stats
+                wav24 = self._normalize(wav24, spans24, loudness, peak_ceiling)
+                if normalise:
+                    rows.append(self.last_loudness)
                 wav, spans = self._convert(wav24, spans24, sample_rate, pcm16)
                 for i, scales in enumerate(chunk):
                     results.append({"scales": scales, "wave": wav[spans[i][0]:spans[i][0] + spans[i][1]], "frames": int(spans24[i][1]) // 384,
                                     "stats_before": before[i], "stats_after": after[i]})
+                    if normalise:
+                        results[-1]["loudness"] = rows[-1][i]
                     if curves is not None:  # (a chunk whose alternatives are all None took the path without curves: no Spans, no blocks)
                         none = np.zeros((0, len(prosody.STATS)), dtype=np.float32)
                         per = self.last_prosody_span_stats
                         results[-1].update(curve=which[lo + i], span_stats=(none, none) if per is None else per[i])
+            if normalise:
+                self.last_loudness = torch.cat(rows)
         return results
 
-    def stream(self, text, input_is_phones=False, chunk_frames=512, halo_frames=None, max_batch=4, z_noise=None, sample_rate=None, pcm16=False, **prosody):
+    def stream(self, text, input_is_phones=False, chunk_frames=512, halo_frames=None, max_batch=4, z_noise=None, sample_rate=None, pcm16=False, loudness=None,
+               peak_ceiling=-1.0, **prosody):
         """Generator of waveform pieces for ONE (long) text: the acoustic model runs once, the vocoder chunk-wise with overlap
         (streaming.py) - the concatenation equals ``self(text, ...)`` bit for bit, the first piece is ready after one chunk and the
         vocoder's workspace is bounded by ``max_batch`` chunks.  prosody: the keyword arguments of ``forward`` (gold durations /
         pitch / energy, scaling factors, ``prosody_curves``).  ``sample_rate`` / ``pcm16``: the pieces at another rate and / or as int16, converted as
-        they come (resample.Resampler.streamer); their concatenation equals ``self(text, sample_rate=..., pcm16=...)`` bit for bit."""
+        they come (resample.Resampler.streamer); their concatenation equals ``self(text, sample_rate=..., pcm16=...)`` bit for bit.
+        ``loudness`` raises ValueError: the integrated loudness is a property of the whole utterance, which a stream does not have."""
+        if loudness is not None:
+            raise ValueError("stream() cannot normalise loudness: the integrated loudness needs the whole utterance; use forward(loudness=...)")
         from . import streaming
         convert = self._check_output_format(sample_rate, pcm16)
         halo = streaming.DEFAULT_HALO if halo_frames is None else halo_frames
@@ -514,13 +581,21 @@ class ToucanTTSInterface(torch.nn.Module):
                      increased_compatibility_mode=False,
                      input_is_phones=False,
                      sample_rate=None,
-                     pcm16=False):
+                     pcm16=False,
+                     loudness=None,
+                     peak_ceiling=-1.0):
         """Same result as the reference's sentence loop (:231-285: silence, sentence, silence, ... with blank strings skipped,
         24 kHz float file or sample-doubled 48 kHz PCM16), but the sentences go through the engines as ragged batches of up to
         MAX_FILE_BATCH utterances and the file is assembled once on the host.  ``sample_rate`` / ``pcm16`` (additive): every
         sentence is converted on the device on its own, the silence is ceil(10600 new / orig) samples and the file has that rate;
         with ``pcm16`` the writer gets the device's int16.  Not with ``increased_compatibility_mode``, which stays the
-        reference's doubling."""
+        reference's doubling.  ``loudness`` / ``peak_ceiling`` (additive, as in ``synthesize_batch``): every sentence is normalised on
+        its own (a measurement of the whole file gates the silences out, but not the blocks that straddle the edge of a sentence: it
+        reads a little below the sentences);
+        ``self.last_loudness`` holds the rows of the spoken sentences in file order.  Not with ``increased_compatibility_mode``."""
+        if increased_compatibility_mode and loudness is not None:
+            raise ValueError("increased_compatibility_mode is the reference's path as it is: it does not combine with loudness")
+        normalise = self._check_loudness(loudness, peak_ceiling)
         if increased_compatibility_mode and (sample_rate is not None or pcm16):
             raise ValueError("increased_compatibility_mode is the reference's sample doubling to 48 kHz PCM16: it does not combine with "
                              "sample_rate / pcm16")
@@ -529,7 +604,7 @@ class ToucanTTSInterface(torch.nn.Module):
         column = lambda lst: list(lst) + [None] * (n - len(lst)) if lst else [None] * n
         durs, pits, enes = column(dur_list), column(pitch_list), column(energy_list)
         spoken = [i for i, t in enumerate(text_list) if t.strip() != ""]
-        pieces = {}
+        pieces, rows = {}, {}
         for lo in range(0, len(spoken), self.MAX_FILE_BATCH):
             chunk = spoken[lo:lo + self.MAX_FILE_BATCH]
             if not silent:
@@ -546,9 +621,14 @@ class ToucanTTSInterface(torch.nn.Module):
                                               pitch=[pits[i] for i in idx] if has_p else None,
                                               energy=[enes[i] for i in idx] if has_e else None,
                                               duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
-                                              energy_variance_scale=energy_variance_scale, sample_rate=sample_rate, pcm16=pcm16)
-                for i, w in zip(idx, waves):
+                                              energy_variance_scale=energy_variance_scale, sample_rate=sample_rate, pcm16=pcm16,
+                                              loudness=loudness, peak_ceiling=peak_ceiling)
+                for r, (i, w) in enumerate(zip(idx, waves)):
                     pieces[i] = w.cpu().numpy()
+                    if normalise:
+                        rows[i] = self.last_loudness[r]
+        if normalise:
+            self.last_loudness = torch.stack([rows[i] for i in spoken]) if spoken else torch.zeros((0, 8), dtype=torch.float64, device=self.device)
         rate = self.SAMPLE_RATE if sample_rate is None else int(sample_rate)
         gap = self.SILENCE_SAMPLES
         if rate != self.SAMPLE_RATE:

@@ -1,0 +1,92 @@
+/*
+ * toucan_loudness.h - C ABI of the loudness meter in libtoucan_hip.so (csrc/loudness.hip): integrated loudness of every utterance
+ * of a ragged batch after ITU-R BS.1770-4 (K-weighting, 400 ms blocks with 75 % overlap, absolute and relative gate) and the gain
+ * that brings it to a target under a sample-peak ceiling.  DESIGN.md section 17 holds the decisions and tests/loudness_ref.py the
+ * float64 restatement.  Same conventions as toucan_resample.h: device pointers owned by the caller, a packed float32 wave, one
+ * (begin, count) span per utterance, one hipStream_t per call, 0 or a negative TTS_E_* code, tts_last_error(); an utterance's
+ * result depends on that utterance alone.  The build's own caller is ims-toucan-prosody-variance_amd/loudness.py (ctypes:
+ * capi.LOUDNESS_PROTOTYPES).
+ *
+ * K-weighting at the sample rate fs: two biquads in cascade, bilinear transforms of the analogue prototypes, computed by the
+ * caller in float64 once per rate.
+ *     shelf:      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196,
+ *                 K = tan(pi f0 / fs), Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *                 b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0],
+ *                 a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *     high-pass:  f0 = 38.13547087602444, Q = 0.5003270373238773, K = tan(pi f0 / fs), d = 1 + K / Q + K^2,
+ *                 b = [1, -2, 1], a = [1, 2 (K^2 - 1) / d, (1 - K / Q + K^2) / d]
+ * At 48 kHz these are the coefficients printed in BS.1770-4; a full-scale 997 Hz sine reads -3.01 LKFS there.
+ *
+ * The recurrence, direct form II transposed, every value fp64, x the float32 sample, state (s1, s2, s3, s4) = 0 at the first
+ * sample of an utterance (b, a the shelf's, c the high-pass's a):
+ *     y1 = fma(b0, x, s1);   s1 = fma(-a1, y1, fma(b1, x, s2));    s2 = fma(-a2, y1, b2 x);
+ *     y2 = y1 + s3;          s3 = fma(-c1, y2, fma(-2, y1, s4));   s4 = fma(-c2, y2, y1);
+ *
+ * Gating.  S = fs / 10 samples are one segment (fs a multiple of 10 in 8 000 .. 192 000); e_k is the sum of y2^2 over segment k,
+ * accumulated in sample order (e = fma(y2, y2, e)); only complete segments count.  Block j covers the segments j .. j + 3:
+ *     z_j = (((e_j + e_{j+1}) + e_{j+2}) + e_{j+3}) / (4 S),     l_j = -0.691 + 10 log10 z_j.
+ * The absolute gate keeps l_j > -70, tested as z_j > 10^((-70 + 0.691) / 10); with m the mean of the z_j it keeps, the relative
+ * gate keeps of those the l_j > -0.691 + 10 log10 m - 10, tested as z_j > m / 10.  The integrated loudness is
+ * -0.691 + 10 log10 (mean of the z_j both gates keep), and -inf for an utterance shorter than four segments or without a block
+ * past the absolute gate.  Every sum runs in index order in fp64.
+ *
+ * Normalisation to the target L_t (LUFS) under the ceiling c (dBFS, a SAMPLE peak: max |x|, not a 4x oversampled true peak):
+ *     g = min(10^((L_t - L) / 20), 10^(c / 20) / peak),    g = 1 where L = -inf or peak = 0,
+ * rounded to float32 once (towards zero as far as needed for float32(peak g) <= 10^(c / 20) where the ceiling is what limits
+ * it); y = x g is one fp32 multiply per sample.
+ */
+#ifndef TOUCAN_LOUDNESS_H
+#define TOUCAN_LOUDNESS_H
+
+#include "toucan_tts.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define TTS_LOUDNESS_MIN_RATE 8000
+#define TTS_LOUDNESS_MAX_RATE 192000
+#define TTS_LOUDNESS_COLUMNS 8      /* lufs, peak, blocks, blocks_abs, blocks_both, momentary_max_lufs, gain, lufs_after */
+#define TTS_LOUDNESS_TABLE_DOUBLES 24 /* shelf b0 b1 b2 a1 a2, high-pass a1 a2, 0, then M row-major */
+
+/* Segments one workgroup of tts_kweight_energy takes (one lane each). */
+int tts_loudness_tile_segments(void);
+
+/* Spans, in all three calls: int64 [batch][2] = (first sample, sample count) of every utterance in the packed wave of n_samples
+ * samples, on the device (`spans`) and the same rows on the host (`spans_host`).  The library checks the host rows before it
+ * launches - count >= 0, 0 <= begin, begin + count <= n_samples; TTS_E_ARG otherwise, the message names the utterance - and the
+ * kernels take a device row that fails the same check as an utterance of no samples, so nothing outside the wave is touched.
+ *
+ * Utterance u has ceil(count / S) segment slots, S = seg_samples = fs / 10; slot k of utterance u is element u * max_segments + k
+ * of energy, peak and state (max_segments >= every utterance's slots, >= 1). */
+
+/* energy[u][k] = e_k (fp64) of every complete segment and peak[u][k] = max |x| (fp32) of every slot; a trailing partial segment
+ * gets its peak and energy 0.  table: TTS_LOUDNESS_TABLE_DOUBLES fp64 on the device: the coefficients above and M, the 4 x 4
+ * zero-input transition of the state over S samples (column i = the state S samples after the unit state i, by the recurrence
+ * above with x = 0).  state: workspace, fp64 [batch][max_segments][4].  Three launches: every segment from the zero state, its
+ * end state kept; per utterance, in order, s_{k+1} = M s_k + end_k (row i: fma(M[i][3], s4, fma(M[i][2], s3, fma(M[i][1], s2,
+ * fma(M[i][0], s1, end_k[i]))))); every segment again from its true start state, accumulating e_k.  Exact up to fp64 rounding -
+ * no truncated warm-up - and one fixed chain per segment: a batch equals its utterances alone bit for bit. */
+int tts_kweight_energy(const float* x, int64_t n_samples, const int64_t* spans, const int64_t* spans_host, int32_t batch,
+                       int32_t seg_samples, const double* table, int64_t max_segments, double* state, double* energy, float* peak,
+                       tts_stream_t stream);
+
+/* stats[u][0 .. 7] (fp64, TTS_LOUDNESS_COLUMNS) from energy and peak: the integrated loudness, max |x| of the utterance, the
+ * number of blocks, of blocks past the absolute gate and past both, the loudest block's l_j (-inf without a block), the gain as
+ * the float32 it is applied as, and lufs + 20 log10 gain.  target_lufs = NaN measures only: gain = 1.  peak_ceiling_dbfs is
+ * ignored then; otherwise both must be finite and the ceiling <= 0 (TTS_E_ARG). */
+int tts_loudness_gate(const double* energy, const float* peak, int64_t n_samples, const int64_t* spans, int32_t batch,
+                      int32_t seg_samples, int64_t max_segments, double target_lufs, double peak_ceiling_dbfs, double* stats,
+                      tts_stream_t stream);
+
+/* y[i] = x[i] * (float)stats[u][6] for every sample i of every span; y has the layout of x and may be x itself; samples outside
+ * every span are not written.  max_count >= every count.  The gain is read on the device: nothing returns to the host between
+ * measuring and applying. */
+int tts_apply_gain(const float* x, int64_t n_samples, const int64_t* spans, const int64_t* spans_host, int32_t batch, int64_t max_count,
+                   const double* stats, float* y, tts_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* TOUCAN_LOUDNESS_H */
