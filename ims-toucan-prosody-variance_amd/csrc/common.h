@@ -59,15 +59,23 @@ struct WavenetCond {
 };
 int wavenet_layer_cond(const TtsWavenetDesc& d, const WavenetCond& c, hipStream_t st);
 
-// The WaveNet of one coupling block in one launch (wavenet.hip): h = start(x0) and the four layers; x in ([rows, >= 80] fp32, the
-// packed rows of the squeezed layout; only x0 = columns 0 .. 79 is read), the block's skip sum out ([rows, 192] fp32).  The start
-// conv as packed for tts_conv1d's 16-bit path ([1][cin_pad / 8][w0_n][8], only its first 192 columns are used), the layers'
-// weights and the conditioning as for wavenet_layer_cond; layer i uses conditioning columns 384 i .. 384 i + 383.  The tile
-// table has wavenet_block_tile_rows() rows per tile.
+// One coupling block of the PostFlow's reverse pass in one launch (wavenet.hip): h = start(x0), the four WaveNet layers, then on
+// the block's skip sum - which never leaves the chip - [m | logs] = end(skip), the coupling x1 = (x1 - m) exp(-logs), the inverse
+// 1x1 conv and ActNorm (glow_invconv_actnorm).  x in ([rows, 160] fp32, the packed rows of the squeezed layout), x_out likewise:
+// a different buffer, because a workgroup reads the x0 halo rows that its neighbours rewrite and the inverse conv changes every
+// channel.  The start conv as packed for tts_conv1d's 16-bit path ([1][cin_pad / 8][w0_n][8], only its first 192 columns are used),
+// the layers' weights and the conditioning as for wavenet_layer_cond; layer i uses conditioning columns 384 i .. 384 i + 383;
+// `end` as packed for tts_conv1d's fp32 path ([192][we_n], m in columns 0 .. 79, logs from column we_half), bias [m | logs].
+// The tile table has wavenet_block_tile_rows() rows per tile.  pad_rows: the n_pad rows of x that lie in no tile (the squeezed
+// row that holds the dropped last frame of an utterance with an odd frame count): they only pass the inverse conv and ActNorm, as
+// they do in glow_invconv_actnorm, which runs over all rows.
 struct WavenetBlock {
   const float* x; int ld_x;
-  float* skip; int ld_skip;
+  float* x_out; int ld_out;
   const void* w0; int w0_n; const float* b0;  // start: 80 -> 192
+  const float* we; int we_n; int we_half; const float* be; float alpha;  // end: 192 -> 2 x 80, fp32; alpha: the conv's output scale
+  const float *winv, *an_bias, *an_logs;      // inverse 1x1 conv [4][4], ActNorm [160]
+  const int* pad_rows; int n_pad;
   const void* w1[4]; const float* b1[4];      // in_layer: packed [5][24][384][8], bias [384]
   const void* w2[4]; const float* b2[4];      // res_skip: packed [1][24][384][8] (last layer [1][24][192][8]), bias
   const float* g; int ld_g;
@@ -138,6 +146,21 @@ __device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
 #define TTS_PIN(r_) asm volatile("" : "+v"(r_))
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
+
+// Glow, reverse pass: the expressions that more than one kernel evaluates, in one place each so that every kernel contracts and
+// rounds them alike (the coupling: tts_conv1d's epilogue and wavenet_block_kernel; the mix: glow_mix_kernel and wavenet_block_kernel).
+//   coupling (Glow.py:301): x1 = (x1 - m) exp(-logs), m and logs with their biases already added
+__device__ __forceinline__ float glow_coupling_value(float ax, float m, float logs) { return (ax - m) * expf(-logs); }
+//   output slot o of a mixing group's inverse 1x1 conv, then ActNorm's inverse (Glow.py:124, :30-31); w = Winv, row-major [4][4];
+//   an_scale = glow_actnorm_scale(logs) of the output channel (a kernel may keep it per channel instead of taking it per element)
+__device__ __forceinline__ float glow_actnorm_scale(float an_logs) { return expf(-an_logs); }
+__device__ __forceinline__ float glow_mix_value(const float (&w)[16], int o, float v0, float v1, float v2, float v3, float an_bias, float an_scale) {
+  float z = w[o * 4 + 0] * v0;
+  z = fmaf(w[o * 4 + 1], v1, z);
+  z = fmaf(w[o * 4 + 2], v2, z);
+  z = fmaf(w[o * 4 + 3], v3, z);
+  return (z - an_bias) * an_scale;
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

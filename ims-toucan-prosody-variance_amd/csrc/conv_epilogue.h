@@ -21,7 +21,7 @@ __device__ __forceinline__ float epilogue_value(const TtsConvDesc& d, float a, f
     } else if (d.mode == TTS_MODE_GATED) {
       v = tanhf(v) * (1.0f / (1.0f + expf(-g)));
     } else {  // COUPLING
-      v = (ax - v) * expf(-g);
+      v = glow_coupling_value(ax, v, g);
     }
   } else {
     if (d.act == TTS_ACT_RELU) v = fmaxf(v, 0.0f);

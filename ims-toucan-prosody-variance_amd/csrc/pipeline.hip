@@ -800,9 +800,11 @@ size_t phone_arena_bytes(size_t R, size_t B) {
          2 * (B + R) * TTS_PROSODY_STATS * 4 + 256;  // (those of tts_control_and_regulate_c: utterances and at most R spans)
 }
 // cond_buffer: the PostFlow keeps the coupling blocks' conditioning [RS, 1536] in memory (every configuration but the 16-bit ones
-// with the fused WaveNet layer, which computes it inside the layer)
+// with the fused WaveNet layer, which computes it inside the layer).  Those configurations run a coupling block as one launch: the
+// [hidden state | skip sum] buffer ([RF / 2, 384]) is not allocated, a second x ([RF / 2, 160]) is: ATT - 80 floats per frame less.
 size_t frame_arena_bytes(size_t RF, bool cond_buffer) {
-  return conformer_bytes(RF) + RF * ((80 + ATT) + 2 * ATT + 3 * 80 + 2 * 256 + ATT + 160 + 4 * ATT + ATT + (cond_buffer ? 8 * ATT : 0) + 64) * 4 + (64 << 20);
+  return conformer_bytes(RF) +
+         RF * ((80 + ATT) + 2 * ATT + 3 * 80 + 2 * 256 + ATT + 160 + 4 * ATT + ATT + (cond_buffer ? 8 * ATT : 0) - (cond_buffer ? 0 : ATT - 80) + 64) * 4 + (64 << 20);
 }
 // vocoder: R packed mel rows.  Arena 1 holds the pre-conv output [R, 512] fp32 and later the stages 1 and 3, arena 0 the stages 0 and 2
 // (a stage reads its input from the other arena).  Per stage: the up-sampled tensor, the stage output and two ping-pong buffers of
@@ -1309,14 +1311,37 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
   const Acoustic& m = h->acoustic;
   TTS_ALLOC(g, a, float, (size_t)RF * ATT);
   TTS_TRY(conv(h, m.g_proj, T2(h->cat, 80 + ATT), T2(g, ATT), h->lf, st));
-  TTS_ALLOC(x, a, float, (size_t)RS * 160);
-  TTS_TRY(hip_ok(hipMemcpyAsync(x, z_noise, (size_t)RS * 160 * 4, hipMemcpyDeviceToDevice, st), "flow noise"));
-  TTS_ALLOC(hs, a, float, (size_t)RS * 2 * ATT);  // [hidden state | skip sum]
-  // 16-bit configurations: one launch for the WaveNet of a block (wavenet_block: start conv and the four layers): it reads x0 and
-  // writes the block's skip sum into the second half of hs; the hidden state never leaves the chip
+  // 16-bit configurations: one launch per coupling block (wavenet_block: start conv, the four layers, end conv with the coupling,
+  // inverse 1x1 conv and ActNorm); the hidden state and the skip sum never leave the chip.  A block reads x from one buffer and
+  // writes the other (its workgroups read each other's rows of x0): block 17 reads z_noise itself, and the 18 writes alternate
+  // between x and x2, so the mel ends in x2 whatever the batch.  The other configurations keep the per-layer launches and x in place.
   const bool fused = !postflow_cond_buffer(h);
+  TTS_ALLOC(x, a, float, (size_t)RS * 160);
+  float *hs = nullptr, *x2 = nullptr;
+  if (fused) {
+    x2 = arena_alloc<float>(a, (size_t)RS * 160);
+  } else {
+    TTS_TRY(hip_ok(hipMemcpyAsync(x, z_noise, (size_t)RS * 160 * 4, hipMemcpyDeviceToDevice, st), "flow noise"));
+    hs = arena_alloc<float>(a, (size_t)RS * 2 * ATT);  // [hidden state | skip sum]
+  }
+  if (!hs && !x2) {
+    set_error("tts_postflow: workspace exhausted");
+    return TTS_E_ARG;
+  }
   TileTab tblk;
-  if (fused) TTS_TRY(tiles_of(h, ls, wavenet_block_tile_rows(), st, &tblk));
+  const int* pad_rows = nullptr;  // the squeezed rows outside every tile: the one behind an utterance with an odd frame count
+  int n_pad = 0;
+  if (fused) {
+    TTS_TRY(tiles_of(h, ls, wavenet_block_tile_rows(), st, &tblk));
+    void* dev;
+    TTS_TRY(table_of(h, layout_key(h->lf, -2), st, [&] {
+      std::vector<int> host;
+      for (int u = 0; u < h->lf.n(); ++u)
+        if (h->lf.lengths[u] & 1) host.push_back(ls.begins[u] + ls.lengths[u]);
+      return host;
+    }, &dev, &n_pad));
+    pad_rows = static_cast<const int*>(dev);
+  }
   // the fused layers compute their conditioning columns themselves: no acts, no cond buffer
   char* acts = nullptr;
   float* cond = nullptr;
@@ -1328,7 +1353,7 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
       return TTS_E_ARG;
     }
   }
-  float* skip = hs + ATT;
+  float* skip = hs ? hs + ATT : nullptr;
   double live_rows = 0;  // (stage profiler)
   for (int n : ls.lengths) live_rows += n;
   for (int b = 17; b >= 0; --b) {
@@ -1345,7 +1370,15 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
                     "tts_postflow: flow.%d.cond is not a 16-bit 1-tap 384 -> 1536 conv", b);
       WavenetBlock w;
       memset(&w, 0, sizeof(w));
-      w.x = x; w.ld_x = 160; w.skip = skip; w.ld_skip = 2 * ATT;
+      TTS_CHECK_ARG(f.end.w && f.end.mode == TTS_MODE_COUPLING && f.end.cin == ATT && f.end.cin_pad == ATT && f.end.cout == 80 && f.end.taps == 1,
+                    "tts_postflow: flow.%d.end is not an fp32 1-tap 192 -> 2 x 80 coupling conv", b);
+      // block 17 reads the noise where the caller put it; the others what the block before them wrote
+      const float* xin = b == 17 ? z_noise : ((b & 1) ? x2 : x);
+      float* xout = (b & 1) ? x : x2;
+      w.x = xin; w.ld_x = 160; w.x_out = xout; w.ld_out = 160;
+      w.we = f.end.w; w.we_n = f.end.wn; w.we_half = f.end.half_pad; w.be = f.end.bias; w.alpha = ConvOpt().alpha;
+      w.winv = f.winv; w.an_bias = f.an_bias; w.an_logs = f.an_logs;
+      w.pad_rows = pad_rows; w.n_pad = n_pad;
       w.w0 = f.start.w16; w.w0_n = f.start.wn; w.b0 = f.start.bias;
       w.g = g; w.ld_g = 2 * ATT; w.wc = cnd.w16; w.wc_n = cnd.wn; w.bc = cnd.bias;
       w.tiles = tblk.dev; w.n_tiles = tblk.n; w.tile_rows = wavenet_block_tile_rows();
@@ -1355,11 +1388,13 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
         TTS_CHECK_ARG(inl.w16 && rs.w16 && inl.compute16 == cnd.compute16 && rs.cout == (i < 3 ? 2 * ATT : ATT), "tts_postflow: flow.%d layer %d is not a 16-bit WaveNet layer", b, i);
         w.w1[i] = inl.w16; w.b1[i] = inl.bias; w.w2[i] = rs.w16; w.b2[i] = rs.bias;
       }
-      // start, and four layers' in-layer, conditioning and res/skip products (the halo's repeated rows are not counted); x0 in, skip
-      // out, g, weights
-      TTS_TRY(prof_launch(h, "wavenet_block", 2.0 * live_rows * (80.0 * ATT + 4.0 * (ATT * 5 * 2 * ATT + 2 * ATT * 2 * ATT) + 3.0 * ATT * 2 * ATT + (double)ATT * ATT),
-                          live_rows * 4.0 * (80 + ATT + 2 * ATT) + 2.0 * (80.0 * ATT + 4.0 * (5 * ATT * 2 * ATT + 2 * ATT * 2 * ATT) + 3.0 * ATT * 2 * ATT + (double)ATT * ATT),
-                          live_rows * ATT, st, [&] { return wavenet_block(w, st); }));
+      // start, four layers' in-layer, conditioning and res/skip products, end and the 4 x 4 mix of 40 groups (the halo's repeated
+      // rows are not counted); x in, x out, g, the 16-bit weights and end's fp32 ones
+      TTS_TRY(prof_launch(h, "wavenet_block",
+                          2.0 * live_rows * (80.0 * ATT + 4.0 * (ATT * 5 * 2 * ATT + 2 * ATT * 2 * ATT) + 3.0 * ATT * 2 * ATT + (double)ATT * ATT + ATT * 160.0 + 160.0 * 4),
+                          live_rows * 4.0 * (160 + 160 + 2 * ATT) + 2.0 * (80.0 * ATT + 4.0 * (5 * ATT * 2 * ATT + 2 * ATT * 2 * ATT) + 3.0 * ATT * 2 * ATT + (double)ATT * ATT) + 4.0 * ATT * 160,
+                          live_rows * 160, st, [&] { return wavenet_block(w, st); }));
+      continue;
     }
     for (int i = 0; i < 4 && !fused; ++i) {
       const ConvW &inl = m.flowgrp[b / 4].inl[i], &rs = m.flowgrp[b / 4].res_skip[i];
@@ -1378,7 +1413,7 @@ int pipeline_postflow(Handle* h, const float* z_noise, hipStream_t st) {
     TTS_TRY(conv(h, f.end, T2(skip, 2 * ATT), T2(x + 80, 160), ls, st, oe));
     TTS_TRY(tts_glow_invconv_actnorm(x, 160, RS, 160, f.winv, f.an_bias, f.an_logs, st));
   }
-  h->mel = x;  // unsqueeze = re-view [2 RS, 80]
+  h->mel = fused ? x2 : x;  // (block 0 wrote x2) unsqueeze = re-view [2 RS, 80]
   h->have_flow = true;
   return TTS_OK;
 }

@@ -236,13 +236,7 @@ __global__ __launch_bounds__(256) void glow_mix_kernel(float* __restrict__ x, in
     const float v0 = xr[i0], v1 = xr[i1], v2 = xr[i2], v3 = xr[i3];
     const int idx[4] = {i0, i1, i2, i3};
 #pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      float z = w[o * 4 + 0] * v0;
-      z = fmaf(w[o * 4 + 1], v1, z);
-      z = fmaf(w[o * 4 + 2], v2, z);
-      z = fmaf(w[o * 4 + 3], v3, z);
-      xr[idx[o]] = (z - an_bias[idx[o]]) * expf(-an_logs[idx[o]]);
-    }
+    for (int o = 0; o < 4; ++o) xr[idx[o]] = glow_mix_value(w, o, v0, v1, v2, v3, an_bias[idx[o]], glow_actnorm_scale(an_logs[idx[o]]));
   }
 }
 

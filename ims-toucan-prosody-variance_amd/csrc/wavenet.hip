@@ -32,7 +32,7 @@
 namespace tts {
 
 namespace {
-constexpr int WN_H = 192;            // hidden channels
+constexpr int WN_H = 192;           // hidden channels
 constexpr int WN_BM = 64;            // frames per workgroup
 constexpr int WN_TAPS = 5;
 constexpr int WN_XP = WN_H + 8;      // LDS pitch of the window / of acts (16-bit elements)
@@ -327,11 +327,12 @@ __global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc
   }
 }
 
-// ---- One coupling block's WaveNet (the start conv and its four layers) in one launch -----------------------------------------
+// ---- One coupling block (the start conv, the four WaveNet layers, end conv + coupling, inverse 1x1 conv + ActNorm) in one launch --
 // h = start(x0) is computed in the workgroup (80 -> 192, five k-steps), then the layer body above, looped: the hidden state and the skip sum stay in the registers of the wavefronts that own their output
 // channels in the res/skip product (waves 0, 1: h; waves 2, 3: skip), the next layer's 16-bit window is written straight from
 // the res/skip epilogue, the squeezed g is staged once for the four conditioning products, and the weight stream runs on from
-// one layer into the next.  Nothing but the block's skip sum is written.  Halo by recomputation: a workgroup computes the 64 rows
+// one layer into the next.  The skip sum is not written either: the tail (below the layer loop) turns it into the block's new x,
+// the only thing the launch writes, into a buffer of its own (x_out), since neighbours read the old x0.  Halo by recomputation: a workgroup computes the 64 rows
 // row0 - 8 .. row0 + 55 through all four layers (each 5-tap layer costs 2 rows a side) and stores the central 48; the tile table
 // has 48-row tiles.  In every layer's window the rows outside the utterance are zeros (the per-layer form's zero padding), also
 // where they lie inside the computed range.  Acts have a buffer of their own, so a layer needs two barriers: the window is
@@ -342,20 +343,44 @@ namespace {
 constexpr int WB_OUT = 48;   // rows stored per workgroup
 constexpr int WB_HALO = 8;   // 4 layers x 2 rows
 constexpr int WB_CIN = 80;   // channels of x0, the start conv's input
+constexpr int WB_COUT = 80;  // channels of x1 = of m and of logs, the halves of the end conv
+constexpr int WB_X = 2 * WB_COUT;  // channels of x
+constexpr int WB_MIXG = WB_X / 4;  // mixing groups of a row
+constexpr int WB_SP = WN_H + 4;    // LDS pitch of the fp32 skip sum (floats): rows 4 banks apart, a 16-lane ds_read_b128 phase is conflict-free
 constexpr size_t WB_AS_BYTES = (size_t)WN_BM * WN_XP * 2;
-constexpr size_t WB_LDS_BYTES = WN_XS_BYTES + WB_AS_BYTES + WN_GS_BYTES;
+constexpr size_t WB_LDS_BYTES = WN_XS_BYTES + WN_GS_BYTES + WB_AS_BYTES;
 static_assert(WB_OUT + 2 * WB_HALO == WN_BM, "stored rows plus the halo are the computed tile");
+static_assert(((size_t)WN_BM * WB_SP + 3 * WB_X) * 4 <= WN_XS_BYTES + WN_GS_BYTES, "the fp32 skip sum and the epilogue's operands fit over the window and the g tile");
 }  // namespace
 
 template <bool F16>
 __global__ __launch_bounds__(256) void wavenet_block_kernel(const WavenetBlock d) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   unsigned short* xs = reinterpret_cast<unsigned short*>(lds_raw);                               // [68][XP] window of h
-  unsigned short* as = reinterpret_cast<unsigned short*>(lds_raw + WN_XS_BYTES);                 // [64][XP] acts
-  unsigned short* gs = reinterpret_cast<unsigned short*>(lds_raw + WN_XS_BYTES + WB_AS_BYTES);  // [64][GP] squeezed g
+  unsigned short* gs = reinterpret_cast<unsigned short*>(lds_raw + WN_XS_BYTES);                 // [64][GP] squeezed g
+  unsigned short* as = reinterpret_cast<unsigned short*>(lds_raw + WN_XS_BYTES + WN_GS_BYTES);  // [64][XP] acts
+  float* sk = reinterpret_cast<float*>(lds_raw);  // the tail: [64][SP] fp32 skip sum, over the window and g (nobody reads them then)
+  const int tid = threadIdx.x, lane = tid & 63, lrow = lane & 31, lk = lane >> 5;
+  // ---- workgroups behind the tile table: the rows of x that belong to no tile.  No coupling reaches them; they pass the inverse
+  // 1x1 conv and ActNorm like every row (glow_mix_kernel's loop, reading x and writing x_out)
+  if ((int)blockIdx.x >= d.n_tiles) {
+    float w[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) w[i] = d.winv[i];
+    const int total = d.n_pad * WB_MIXG;
+    for (int e = ((int)blockIdx.x - d.n_tiles) * 256 + tid; e < total; e += ((int)gridDim.x - d.n_tiles) * 256) {
+      const int r = d.pad_rows[e / WB_MIXG], g = e % WB_MIXG;
+      const float* xr = d.x + (size_t)r * d.ld_x;
+      float* orow = d.x_out + (size_t)r * d.ld_out;
+      const int idx[4] = {2 * g, 2 * g + 1, WB_COUT + 2 * g, WB_COUT + 2 * g + 1};
+      const float v0 = xr[idx[0]], v1 = xr[idx[1]], v2 = xr[idx[2]], v3 = xr[idx[3]];
+#pragma unroll
+      for (int o = 0; o < 4; ++o) orow[idx[o]] = glow_mix_value(w, o, v0, v1, v2, v3, d.an_bias[idx[o]], glow_actnorm_scale(d.an_logs[idx[o]]));
+    }
+    return;
+  }
   const TtsTile tile = d.tiles[blockIdx.x];
   const int c0 = tile.row0 - WB_HALO;  // first computed row
-  const int tid = threadIdx.x, lane = tid & 63, lrow = lane & 31, lk = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int P0 = (wave * 5 + 1) / 3, P1 = wave < 2 ? 1 : 4, fP = wave & 1, fQ = fP ^ 1;
   auto clamp_row = [&](int gr) __attribute__((always_inline)) { return gr < tile.seq_begin ? tile.seq_begin : (gr >= tile.seq_end ? tile.seq_end - 1 : gr); };
@@ -618,16 +643,167 @@ __global__ __launch_bounds__(256) void wavenet_block_kernel(const WavenetBlock d
     TTS_PIN(wr[u][2]);
     TTS_PIN(wr[u][3]);
   }
-  // ---- the block's skip sum: the central rows of the tile, inside the utterance
+  // ---- the tail: [m | logs] = end(skip sum), the coupling, the inverse 1x1 conv and ActNorm; the new x is all that is written.
+  // `end` in the arithmetic of the stand-alone launch (gemm_rows_kernel's fp32 branch in conv1d.hip): v_mfma_f32_32x32x2_f32 with
+  // the weights as the first operand, one accumulator chain per output half, channel groups g ascending, MFMA j of a group
+  // contracting channels 8 g + j and 8 g + 4 + j.  Wave cb = 0, 1, 2 owns output columns 32 cb .. 32 cb + 31 of both halves over
+  // both frame blocks (of block 2 only columns 64 .. 79 are real; wave 3 has nothing to do), so every weight is fetched once per
+  // workgroup and feeds two MFMAs, m and logs of an element meet in one lane, and a lane's four consecutive columns n .. n + 3 are
+  // the x1 inputs of the two mixing groups n / 2 and n / 2 + 1, whose x0 inputs are columns n .. n + 3 of x: the mix needs no other
+  // lane.  A row's values depend on that row of the skip sum alone, so the halo rows' results are simply not stored.
+  // The weights are fp32 [192][we_n]: a lane's operand is one dword per (row, half), eight loads per group.  They run as a stream
+  // like the layers' (inline-asm loads, counted waits), WE_DEPTH groups ahead: left to the compiler, the loads were scheduled next
+  // to their uses and every group paid an L2 round trip (the launch took 141 us with them, 121 us with the stream; 104 us is the launch
+  // without the tail).  The rows of x the epilogue needs are requested in front of the stream, so its first wait covers them.  The
+  // requests follow the skip sum's way into LDS: issued in front of it, while the state registers are still live, the kernel spilled.
+  constexpr int NF = 2, NG = WN_H / 8, WE_DEPTH = 4, WE_L = 8, XL = NF * 4 * 2;
+  static_assert(NG % WE_DEPTH == 0 && XL + WE_DEPTH * WE_L < 64, "whole blocks of groups; the loads in flight fit the vmcnt counter");
+  const int cb = wave;
+  u32x4 x0u[NF][4], axu[NF][4];  // the rows of x the epilogue needs: requested in front of the stream, so its first wait covers them
+  unsigned int wv[WE_DEPTH][2][4];
+  const char* wq = reinterpret_cast<const char*>(d.we + (size_t)(4 * lk) * d.we_n + cb * 32 + lrow);  // rows 8 g + 4 lk + j, this lane's column
+  const size_t wrow = (size_t)d.we_n * 4, whalf = (size_t)d.we_half * 4;
+  size_t wstep = 8 * wrow;
+  auto wrequest = [&](int slot) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      TTS_GLOAD32(wv[slot][0][j], wq + j * wrow);
+      TTS_GLOAD32(wv[slot][1][j], wq + j * wrow + whalf);
+    }
+    wq += wstep;
+  };
+  // the epilogue's per-channel operands [end bias m | logs][ActNorm bias][exp(-ActNorm logs)] go through LDS (behind the skip sum): read
+  // from memory in the epilogue, each group of four columns paid a round trip behind the stores of the group before it
+  // (staged by wave 3, which has no part in the product and no loads of the stream in flight)
+  float* ep = sk + WN_BM * WB_SP;
+  // The skip sum crosses LDS once, in fp32 (waves 2, 3 each hold half of its channels); every wave has passed the last layer's
+  // barrier (2), so the window and g are free, and acts, which slower waves may still read, are not touched.
   if (wave >= 2) {
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-      const int cb = 3 * (wave - 2) + (j >> 1), t = ((j & 1) ? fQ : fP) * 32 + lrow, row = c0 + t;
-      if (t < WB_HALO || t >= WB_HALO + WB_OUT || row >= tile.seq_end) continue;
-      float* orow = d.skip + (size_t)row * d.ld_skip + cb * 32 + 4 * lk;
+      const int sb = 3 * (wave - 2) + (j >> 1), t = ((j & 1) ? fQ : fP) * 32 + lrow;
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq)
-        *reinterpret_cast<float4*>(orow + 8 * rq) = make_float4(st[j][4 * rq], st[j][4 * rq + 1], st[j][4 * rq + 2], st[j][4 * rq + 3]);
+        *reinterpret_cast<float4*>(sk + t * WB_SP + sb * 32 + 8 * rq + 4 * lk) = make_float4(st[j][4 * rq], st[j][4 * rq + 1], st[j][4 * rq + 2], st[j][4 * rq + 3]);
+    }
+  }
+  if (wave < 3) {
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+      const float* xr = d.x + (size_t)clamp_row(c0 + i * 32 + lrow) * d.ld_x;
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        int n = cb * 32 + 8 * rq + 4 * lk;
+        n = n < WB_COUT ? n : WB_COUT - 4;  // (block 2: the columns past 79 load real ones and are dropped)
+        TTS_GLOAD128(x0u[i][rq], xr + n);
+        TTS_GLOAD128(axu[i][rq], xr + WB_COUT + n);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < WE_DEPTH; ++u) wrequest(u);
+  }
+  if (wave == 3) {
+#pragma unroll 1
+    for (int e = lane; e < 3 * WB_X / 4; e += 64) {
+      const int which = e / (WB_X / 4), c4 = 4 * (e % (WB_X / 4));
+      float4 v = *reinterpret_cast<const float4*>((which == 0 ? d.be : (which == 1 ? d.an_bias : d.an_logs)) + c4);
+      if (which == 2) v = make_float4(glow_actnorm_scale(v.x), glow_actnorm_scale(v.y), glow_actnorm_scale(v.z), glow_actnorm_scale(v.w));
+      *reinterpret_cast<float4*>(ep + 4 * e) = v;
+    }
+  }
+  publish();  // (3) the skip sum is complete
+  if (wave < 3) {
+    auto u2f = [](unsigned int bits) __attribute__((always_inline)) { return __builtin_bit_cast(float, bits); };
+    f32x16 am[NF], al[NF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        am[i][r] = 0.0f;
+        al[i][r] = 0.0f;
+      }
+    const float* skr = sk + lrow * WB_SP + 4 * lk;
+#pragma unroll 1
+    for (int base = 0; base < NG; base += WE_DEPTH) {
+      if (base == NG - WE_DEPTH) {  // nothing follows: the tail re-requests the last group (unused), no branch in the stream
+        wq -= wstep;
+        wstep = 0;
+      }
+#pragma unroll
+      for (int u = 0; u < WE_DEPTH; ++u) {
+        float4 bq[NF];
+#pragma unroll
+        for (int i = 0; i < NF; ++i) bq[i] = *reinterpret_cast<const float4*>(skr + i * 32 * WB_SP + 8 * (base + u));
+        TTS_WAIT_VM((WE_DEPTH - 1) * WE_L);
+        float wm[4], wl[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          TTS_PIN(wv[u][0][j]);
+          TTS_PIN(wv[u][1][j]);
+          wm[j] = u2f(wv[u][0][j]);  // copies: the slot is re-requested below while the MFMAs may still read
+          wl[j] = u2f(wv[u][1][j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int i = 0; i < NF; ++i) {
+            const float bv = j == 0 ? bq[i].x : (j == 1 ? bq[i].y : (j == 2 ? bq[i].z : bq[i].w));
+            am[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(wm[j], bv, am[i], 0, 0, 0);
+            al[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(wl[j], bv, al[i], 0, 0, 0);
+          }
+        wrequest(u);
+      }
+    }
+    TTS_WAIT_VM(0);  // drain the tail requests
+#pragma unroll
+    for (int u = 0; u < WE_DEPTH; ++u)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        TTS_PIN(wv[u][0][j]);
+        TTS_PIN(wv[u][1][j]);
+      }
+    float4 x0v[NF][4], axv[NF][4];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        TTS_PIN(x0u[i][rq]);
+        TTS_PIN(axu[i][rq]);
+        const u32x4 p = x0u[i][rq], q = axu[i][rq];
+        x0v[i][rq] = make_float4(u2f(p[0]), u2f(p[1]), u2f(p[2]), u2f(p[3]));
+        axv[i][rq] = make_float4(u2f(q[0]), u2f(q[1]), u2f(q[2]), u2f(q[3]));
+      }
+    float w[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) w[i] = d.winv[i];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+      const int t = i * 32 + lrow, row = c0 + t;
+      if (t < WB_HALO || t >= WB_HALO + WB_OUT || row >= tile.seq_end) continue;
+      float* orow = d.x_out + (size_t)row * d.ld_out;
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const int n = cb * 32 + 8 * rq + 4 * lk;
+        if (n >= WB_COUT) continue;
+        const float4 bm = *reinterpret_cast<const float4*>(ep + n), bl = *reinterpret_cast<const float4*>(ep + WB_COUT + n);
+        const float bmv[4] = {bm.x, bm.y, bm.z, bm.w}, blv[4] = {bl.x, bl.y, bl.z, bl.w};
+        const float axq[4] = {axv[i][rq].x, axv[i][rq].y, axv[i][rq].z, axv[i][rq].w};
+        float y[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {  // epilogue_value<true> of the coupling conv (conv_epilogue.h): no per-utterance vector, no pre-add, no residual
+          const float m = am[i][4 * rq + q] + bmv[q] + 0.0f, logs = al[i][4 * rq + q] + blv[q];
+          y[q] = glow_coupling_value(axq[q], m, logs);
+          y[q] *= d.alpha;
+        }
+        // mixing groups n / 2 and n / 2 + 1: slots (x0[n], x0[n + 1], x1[n], x1[n + 1]) and (x0[n + 2], x0[n + 3], x1[n + 2], x1[n + 3])
+        const float4 b0 = *reinterpret_cast<const float4*>(ep + WB_X + n), b1 = *reinterpret_cast<const float4*>(ep + WB_X + WB_COUT + n);
+        const float4 l0 = *reinterpret_cast<const float4*>(ep + 2 * WB_X + n), l1 = *reinterpret_cast<const float4*>(ep + 2 * WB_X + WB_COUT + n);
+        const float4 xa = x0v[i][rq];
+        *reinterpret_cast<float4*>(orow + n) = make_float4(glow_mix_value(w, 0, xa.x, xa.y, y[0], y[1], b0.x, l0.x), glow_mix_value(w, 1, xa.x, xa.y, y[0], y[1], b0.y, l0.y),
+                                                           glow_mix_value(w, 0, xa.z, xa.w, y[2], y[3], b0.z, l0.z), glow_mix_value(w, 1, xa.z, xa.w, y[2], y[3], b0.w, l0.w));
+        *reinterpret_cast<float4*>(orow + WB_COUT + n) = make_float4(glow_mix_value(w, 2, xa.x, xa.y, y[0], y[1], b1.x, l1.x), glow_mix_value(w, 3, xa.x, xa.y, y[0], y[1], b1.y, l1.y),
+                                                                     glow_mix_value(w, 2, xa.z, xa.w, y[2], y[3], b1.z, l1.z), glow_mix_value(w, 3, xa.z, xa.w, y[2], y[3], b1.w, l1.w));
+      }
     }
   }
 }
@@ -675,7 +851,14 @@ int wavenet_launch(const TtsWavenetDesc& d, const WavenetCond* c, hipStream_t st
 int wavenet_block_tile_rows() { return WB_OUT; }
 
 int wavenet_block(const WavenetBlock& d, hipStream_t st) {
-  TTS_CHECK_ARG(d.x && d.w0 && d.b0 && d.skip && d.g && d.wc && d.bc && d.tiles, "wavenet_block: null pointer");
+  TTS_CHECK_ARG(d.x && d.w0 && d.b0 && d.x_out && d.g && d.wc && d.bc && d.tiles, "wavenet_block: null pointer");
+  TTS_CHECK_ARG(d.we && d.be && d.winv && d.an_bias && d.an_logs, "wavenet_block: null pointer (end conv, inverse 1x1 conv or ActNorm)");
+  TTS_CHECK_ARG(d.x_out != d.x, "wavenet_block: x cannot be updated in place (a workgroup reads its neighbours' rows of x0, and the inverse 1x1 conv changes every channel)");
+  TTS_CHECK_ARG(((uintptr_t)d.we & 15) == 0 && ((uintptr_t)d.be & 15) == 0 && ((uintptr_t)d.winv & 15) == 0 && ((uintptr_t)d.an_bias & 15) == 0 &&
+                    ((uintptr_t)d.an_logs & 15) == 0 && ((uintptr_t)d.x_out & 15) == 0,
+                "wavenet_block: x_out, the end conv, the inverse 1x1 conv and ActNorm must be 16-byte aligned");
+  TTS_CHECK_ARG(d.we_half >= 96 && d.we_n >= d.we_half + 96, "wavenet_block: the end conv has %d packed columns (logs from %d): three blocks of 32 per half are read", d.we_n, d.we_half);
+  TTS_CHECK_ARG(d.n_pad >= 0 && (d.n_pad == 0 || d.pad_rows), "wavenet_block: %d rows outside the tiles, no row table", d.n_pad);
   for (int i = 0; i < 4; ++i) {
     TTS_CHECK_ARG(d.w1[i] && d.b1[i] && d.w2[i] && d.b2[i], "wavenet_block: null weights of layer %d", i);
     TTS_CHECK_ARG(((uintptr_t)d.w1[i] & 15) == 0 && ((uintptr_t)d.w2[i] & 15) == 0 && ((uintptr_t)d.b1[i] & 15) == 0 && ((uintptr_t)d.b2[i] & 15) == 0,
@@ -683,13 +866,14 @@ int wavenet_block(const WavenetBlock& d, hipStream_t st) {
   }
   TTS_CHECK_ARG(d.compute == TTS_COMPUTE_BF16 || d.compute == TTS_COMPUTE_F16, "wavenet_block: 16-bit MFMA configurations only (compute %d)", d.compute);
   TTS_CHECK_ARG(d.tile_rows == WB_OUT, "wavenet_block: tile table must use %d rows, got %d", WB_OUT, d.tile_rows);
-  TTS_CHECK_ARG(d.ld_x >= WB_CIN && (d.ld_x & 3) == 0 && d.ld_skip >= WN_H && (d.ld_skip & 3) == 0 && d.ld_g >= WN_G && (d.ld_g & 3) == 0 &&
-                    ((uintptr_t)d.x & 15) == 0 && ((uintptr_t)d.skip & 15) == 0 && ((uintptr_t)d.g & 15) == 0 && ((uintptr_t)d.wc & 15) == 0 && ((uintptr_t)d.bc & 15) == 0 &&
+  TTS_CHECK_ARG(d.ld_x >= WB_X && (d.ld_x & 3) == 0 && d.ld_out >= WB_X && (d.ld_out & 3) == 0 && d.ld_g >= WN_G && (d.ld_g & 3) == 0 &&
+                    ((uintptr_t)d.x & 15) == 0 && ((uintptr_t)d.g & 15) == 0 && ((uintptr_t)d.wc & 15) == 0 && ((uintptr_t)d.bc & 15) == 0 &&
                     ((uintptr_t)d.w0 & 15) == 0 && ((uintptr_t)d.b0 & 15) == 0,
                 "wavenet_block: rows, start and conditioning operands must be 16-byte aligned");
   TTS_CHECK_ARG(d.w0_n >= WN_H, "wavenet_block: the start conv has %d packed columns, the hidden state %d", d.w0_n, WN_H);
   TTS_CHECK_ARG(d.wc_n >= 8 * WN_H, "wavenet_block: %d conditioning columns, four layers need %d", d.wc_n, 8 * WN_H);
-  if (d.n_tiles == 0) return TTS_OK;
+  const int pad_blocks = (d.n_pad * WB_MIXG + 255) / 256;  // workgroups behind the tile table, for the rows outside the tiles
+  if (d.n_tiles + pad_blocks == 0) return TTS_OK;
   const bool f16 = d.compute == TTS_COMPUTE_F16;
   static unsigned long long raised[2] = {0, 0};
   const void* k = f16 ? reinterpret_cast<const void*>(wavenet_block_kernel<true>) : reinterpret_cast<const void*>(wavenet_block_kernel<false>);
@@ -697,8 +881,8 @@ int wavenet_block(const WavenetBlock& d, hipStream_t st) {
     set_error("wavenet_block: raising the dynamic LDS limit failed");
     return TTS_E_LAUNCH;
   }
-  if (f16) hipLaunchKernelGGL((wavenet_block_kernel<true>), dim3(d.n_tiles), dim3(256), WB_LDS_BYTES, st, d);
-  else hipLaunchKernelGGL((wavenet_block_kernel<false>), dim3(d.n_tiles), dim3(256), WB_LDS_BYTES, st, d);
+  if (f16) hipLaunchKernelGGL((wavenet_block_kernel<true>), dim3(d.n_tiles + pad_blocks), dim3(256), WB_LDS_BYTES, st, d);
+  else hipLaunchKernelGGL((wavenet_block_kernel<false>), dim3(d.n_tiles + pad_blocks), dim3(256), WB_LDS_BYTES, st, d);
   return launch_status("wavenet_block");
 }
 

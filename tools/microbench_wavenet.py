@@ -1,6 +1,7 @@
 """Micro-benchmark of tts_wavenet_layer vs the two-launch form at the bench shape (32 utterances x 320 squeezed frames).
-`--block [batch]`: the one-launch WaveNet block of the native PostFlow (wavenet_block: start conv + four layers) instead, timed by the
-stage profiler (HIP events around each of its 18 launches inside tts_postflow) beside the whole stage."""
+`--block [batch]`: the one-launch coupling block of the native PostFlow (wavenet_block: start conv, four layers, end conv with the
+coupling, inverse 1x1 conv and ActNorm) instead, timed alone by the stage profiler (HIP events around each of its 18 launches
+inside tts_postflow, which in the 16-bit configurations launches nothing else per block)."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,7 +13,7 @@ from ims_toucan_prosody_variance_amd.ragged import Ragged
 
 
 def block(B):
-    """wavenet_block inside tts_postflow: B utterances of 128 phonemes x 5 frames (320 squeezed rows each), bf16, fixture weights."""
+    """wavenet_block (the whole coupling block) inside tts_postflow: B utterances of 128 phonemes x 5 frames (320 squeezed rows each), bf16, fixture weights."""
     from ims_toucan_prosody_variance_amd import fixture_weights as fw, native, synthetic as syn
     dev = torch.device("cuda:0")
     pipe = native.NativePipeline(fw.acoustic_state_dict(), None, None, dev, precision="bf16")
