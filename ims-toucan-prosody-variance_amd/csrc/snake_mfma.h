@@ -17,8 +17,13 @@
 // the register-streamed form (snake_stream in snake.h), and the matrix pipe runs beside the VALU.
 //
 // Both filters run in fp16 whatever the conv precision: bf16 activations are exact in fp16 (8-bit mantissa into 11; the vocoder's
-// activations are O(1), far inside fp16's range), the taps carry 2^-12 relative error and s is rounded to 11 bits - all well below
-// the 8-bit rounding of the bf16 conv operand this feeds.
+// activations are O(1), far inside fp16's range), the taps carry up to 2^-12 relative error and s is rounded to 11 bits.  For
+// the bf16 conv operand this feeds, that is below its 8-bit rounding: the residual step's error against float64 is 0.90 - 0.93 of
+// what the model with fp32 filters gives (conv1's output also waits in fp16, not bf16).  For COMPUTE_F16 it is NOT small: the
+// operand has the same 11 bits, and the step's rms error is 1.23 (C = 64, asymmetric test filter) to 1.96 - 2.21 times (C = 32 /
+// 128, Kaiser design) that of fp32 filters: 7.7e-4 of the output's rms instead of 3.5e-4.  Most of it is systematic: the design's
+// fp16 taps sum to 1 - 2.3e-4, each FIR has that DC gain, and the step's output carries a gain of -4.2e-4 (-2.6e-4 to -3.7e-4 in
+// bf16).  Measured on the MI355X by tests/test_gpu_error_budget.py; DESIGN.md section 4, "Error budgets of the 16-bit kernels".
 //
 // Utterance edges: the reference replicate-pads x (5 | 5) before the up-sampler and s (5 | 6) before the decimator.  Replicate
 // padding is linear, so it folds into the constants: a step whose reach leaves [0, T) rebuilds U / D with the out-of-range taps

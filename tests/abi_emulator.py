@@ -104,8 +104,40 @@ def _snake_seq(X, alpha, beta, filt):
     return np.stack([(sp[2 * t:2 * t + 12] * f[:, None]).sum(0) for t in range(T)], 0)
 
 
+def _snake_fir_matrices(T, filt):
+    """The two FIR filters of Activation1d on one utterance of T frames as dense matrices, replicate padding folded onto the edge
+    samples as csrc/snake_mfma.h's gen_up / gen_down fold it (fp32 sums of the taps that meet one sample):
+    U [2 T, T] with u = U x (the factor 2 included), D [T, 2 T] with y = D s."""
+    f = np.asarray(filt, dtype=np.float32)
+    U, D = np.zeros((2 * T, T), np.float32), np.zeros((T, 2 * T), np.float32)
+    qo, t = np.arange(T), np.arange(T)
+    for p in range(2):
+        for e in range(6):  # p = 0: d = e - 3, tap 11 - 2 e;  p = 1: d = e - 2, tap 10 - 2 e
+            np.add.at(U, (2 * qo + p, np.clip(qo + e - 3 + p, 0, T - 1)), f[10 - 2 * e] if p else f[11 - 2 * e])
+    for k in range(12):
+        np.add.at(D, (t, np.clip(2 * t + k - 5, 0, 2 * T - 1)), f[k])
+    return np.float32(2.0) * U, D
+
+
+def _snake_seq_mfma(X, alpha, beta, filt):
+    """_snake_seq with the rounding points of the matrix-core snake (csrc/snake_mfma.h:19-26, 63-67, 154-163, 209-210): the constants
+    U and D and the 2x-rate samples s are fp16, both products accumulate in fp32 (float64 here).  X [T, c] holds fp16 values."""
+    U, D = (_round16(m, True).astype(np.float64) for m in _snake_fir_matrices(X.shape[0], filt))
+    ea = np.exp(alpha.astype(np.float64))
+    ib = 1.0 / (np.exp(beta.astype(np.float64)) + 1e-9)
+    u = U @ X
+    s = _round16((u + ib * np.sin(u * ea) ** 2).astype(np.float32), True).astype(np.float64)
+    return D @ s
+
+
 class Emulator:
-    def __init__(self):
+    def __init__(self, mfma_snake=False):
+        """mfma_snake: model the rounding points that tts_resblock_step's matrix-core snake (C <= 128) adds to the ones in
+        tts_resblock_step's docstring.  csrc/resblock.hip:403-415 stores the raw x of act1 as an fp16 LDS image (`pack16<true>`, exact
+        for 16-bit x) and :677-690 rounds conv1's output to fp16 in both formats (`as_f16`); csrc/snake_mfma.h:19-26 keeps the filter
+        constants and the 2x-rate samples s in fp16 (see _snake_seq_mfma).  Off (the default), the model is the one the VALU snake
+        follows: fp32 x, fp32 taps, fp32 s, conv1's output in the compute format."""
+        self.mfma_snake = bool(mfma_snake)
         self._real = None
         self._err = b""
         self.calls = {}
@@ -302,7 +334,13 @@ class Emulator:
         snake = d.act == capi.PRE_SNAKE
         filt = _arr(d.filt, 12) if snake else None
 
+        mfma = snake and self.mfma_snake and C_ <= 128
+        r16x = (lambda a: _round16(a.astype(np.float32), True).astype(np.float64)) if mfma else (lambda a: a)  # the fp16 image of act1's x
+        rnd_t = (lambda a: _round16(a, True)) if mfma else rnd  # conv1's output ahead of the matrix-core act2: fp16 in both formats
+
         def act(v, al, be):
+            if mfma:
+                return _snake_seq_mfma(v, _arr(al, C_), _arr(be, C_), filt)
             if snake:
                 return _snake_seq(v, _arr(al, C_), _arr(be, C_), filt)
             return np.where(v > 0, v, v * np.float64(np.float32(d.slope)))
@@ -316,10 +354,10 @@ class Emulator:
 
         for sb, se, sid in _seqs_from_tiles(_tiles(d.tiles, d.n_tiles)):
             x = _load(d.x, sb, se, C_, d.ldx, io).astype(np.float64)
-            a1 = rnd(act(x, d.alpha1, d.beta1).astype(np.float32)).astype(np.float64)
+            a1 = rnd(act(r16x(x), d.alpha1, d.beta1).astype(np.float32)).astype(np.float64)
             t = conv(a1, w1, d.dil) + b1
             if snake:
-                t = rnd(t.astype(np.float32)).astype(np.float64)
+                t = rnd_t(t.astype(np.float32)).astype(np.float64)
                 a2 = rnd(act(t, d.alpha2, d.beta2).astype(np.float32)).astype(np.float64)
             else:
                 a2 = rnd(act(t, None, None).astype(np.float32)).astype(np.float64)
