@@ -18,7 +18,7 @@ The reference's on-line fine-tuning of the aligner on the utterance (five SGD st
 it per utterance on the kernels of csrc/train.hip (finetune.py) and aligns on the fine-tuned logits.
 
 Not reproduced: grapheme-to-phoneme conversion (the transcript is a phoneme string),
-and the silero voice-activity trim (``speech_bounds`` gives the speech span instead).  Praat itself is not reproduced bit for bit:
+and the silero voice-activity trim (``speech_bounds`` gives the speech span instead, or has the P.56 activity meter find it).  Praat itself is not reproduced bit for bit:
 ``f0="track"`` runs a restatement of its published algorithm (pitch.py).
 """
 import json
@@ -415,18 +415,57 @@ class ProsodyExtractor:
         return out
 
 
+DETECT = "detect"  # speech_bounds: find the speech with the P.56 activity meter (activity.py) instead of taking a given span
+DETECT_LEAD = 480  # samples at 16 kHz the detected begin is moved back: 30 ms, the envelope's rise time (silero's speech_pad_ms)
+
+
+def detect_speech_bounds(extractor, waves16, names=None):
+    """(start, end) of the speech in every normalised 16 kHz wave: one packed batch through activity.SpeechActivity.measure on the
+    extractor's device, ``activity.bounds`` with a lead of DETECT_LEAD samples.  ValueError naming the utterance without speech."""
+    from . import activity
+    if getattr(extractor, "_activity", None) is None:
+        extractor._activity = activity.SpeechActivity(extractor.device)
+    meter = extractor._activity
+    packed = torch.from_numpy(np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1) for w in waves16] + [np.zeros(0, dtype=np.float32)]))
+    spans, at = [], 0
+    for w in waves16:
+        spans.append((at, len(w)))
+        at += len(w)
+    found = activity.bounds(meter.measure(packed.to(meter.device), spans, style.SR), lead=DETECT_LEAD)
+    for i, b in enumerate(found):
+        if b is None:
+            raise ValueError(f"speech_bounds=\"detect\": no speech found in utterance {i if names is None else names[i]} "
+                             f"({len(waves16[i])} samples at {style.SR} Hz): its envelope never reaches the lowest threshold of ITU-T P.56")
+    return found
+
+
 def extract_prosody_batch(extractor, phone_strings, waves, sr, f0=None, speech_bounds=None, fine_tune=None):
     """Per utterance (durations, pitch or None, energy, start_silence, end_silence), as UtteranceCloner.extract_prosody returns them.
     waves: recordings at `sr` (a list, or one array per utterance); f0: optional frame-level tracks (Hz, 0 = unvoiced, hop 256 at
     16 kHz), or "track" (for all, or in place of an utterance's track) to compute them on the device from the speech span;
     speech_bounds: optional (start, end) sample indices of the speech in the normalised 16 kHz wave - the silero trim's
-    result - else the whole wave is speech and both silences are 0; fine_tune: None, or per utterance a seed or explicit dropout masks
-    for the on-line fine-tuning of the aligner (ProsodyExtractor.extract)."""
+    result - else the whole wave is speech and both silences are 0; "detect" (for all, or in place of an utterance's pair) finds
+    them on the device with the ITU-T P.56 activity meter (activity.py: not silero, and its agreement with the ITU's sv56 is
+    unpinned) and uses them exactly as given ones, ValueError for an utterance without speech; fine_tune: None, or per utterance a
+    seed or explicit dropout masks for the on-line fine-tuning of the aligner (ProsodyExtractor.extract)."""
     srs = sr if isinstance(sr, (list, tuple)) else [sr] * len(waves)
+    norms = [style.normalize_reference_audio(w, r) for w, r in zip(waves, srs)]
+    if isinstance(speech_bounds, str):
+        if speech_bounds != DETECT:
+            raise ValueError(f"speech_bounds takes (start, end) pairs or {DETECT!r}, not {speech_bounds!r}")
+        speech_bounds = [DETECT] * len(norms)
+    if speech_bounds is not None:
+        speech_bounds = list(speech_bounds)
+        for b, v in enumerate(speech_bounds):
+            if isinstance(v, str) and v != DETECT:
+                raise ValueError(f"speech_bounds takes (start, end) pairs or {DETECT!r}, not {v!r} (utterance {b})")
+        which = [b for b, v in enumerate(speech_bounds[:len(norms)]) if isinstance(v, str)]
+        if which:
+            for b, found in zip(which, detect_speech_bounds(extractor, [norms[b] for b in which], names=which)):
+                speech_bounds[b] = found
     feats, spans, sil = [], [], []
-    for b, (ph, w, r) in enumerate(zip(phone_strings, waves, srs)):
+    for b, (ph, norm) in enumerate(zip(phone_strings, norms)):
         feats.append(phones_to_features(ph, handle_missing=False) if isinstance(ph, str) else np.asarray(ph, dtype=np.float32))
-        norm = style.normalize_reference_audio(w, r)
         s, e = (0, len(norm)) if speech_bounds is None or speech_bounds[b] is None else (int(speech_bounds[b][0]), int(speech_bounds[b][1]))
         spans.append(norm[s:e])
         sil.append((s, len(norm) - e))

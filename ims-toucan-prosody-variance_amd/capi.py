@@ -285,6 +285,16 @@ LOUDNESS_PROTOTYPES = {
 # include/toucan_loudness.h TTS_LOUDNESS_MIN_RATE, _MAX_RATE, _COLUMNS, _TABLE_DOUBLES
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE, LOUDNESS_N_COLUMNS, LOUDNESS_TABLE_DOUBLES = 8000, 192000, 8, 24
 
+# symbol -> (restype, argtypes); mirrors include/toucan_activity.h (ITU-T P.56 active speech level, runs of speech: csrc/activity.hip) one to one
+ACTIVITY_PROTOTYPES = {
+    "tts_activity_tile_segments": (C.c_int, []),
+    "tts_activity_envelope": (C.c_int, [_p, _l, _p, _p, _i, _i, _p, _l, _p, _p, _p, _p, _p]),
+    "tts_activity_level": (C.c_int, [_p, _p, _p, _l, _p, _i, _i, _l, C.c_double, C.c_double, _p, _p, _p, _p]),
+    "tts_activity_runs": (C.c_int, [_p, _l, _p, _p, _i, _i, _p, _l, _p, _p, _i, _p, _p, _p, _p]),
+}
+# include/toucan_activity.h TTS_ACTIVITY_MIN_RATE, _MAX_RATE, _COLUMNS, _THRESHOLDS, _COUNTS, _TABLE_DOUBLES
+ACTIVITY_MIN_RATE, ACTIVITY_MAX_RATE, ACTIVITY_N_COLUMNS, ACTIVITY_THRESHOLDS, ACTIVITY_COUNTS, ACTIVITY_TABLE_DOUBLES = 8000, 192000, 8, 15, 16, 6
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -310,7 +320,7 @@ def lib():
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
             list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()) + \
-            list(LOUDNESS_PROTOTYPES.items()):
+            list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -5,7 +5,7 @@ Stated deviations: the transcript is a phoneme string (no G2P o
 accepted with a one-time warning and not performed (the reference's five SGD steps of CTC training), so the result is that of the
 eval-mode aligner - an instance made with ``fine_tune_aligner=True`` performs it on the GPU (finetune.py), per utterance from the
 checkpoint's weights, with dropout masks drawn from ``torch.Generator(fine_tune_seed)`` as the reference draws them on a CPU device
-(or given as ``dropout_masks=``); there is no silero voice-activity trim (the silences are 0 unless ``speech_bounds`` gives the speech span);
+(or given as ``dropout_masks=``); there is no silero voice-activity trim (the silences are 0 unless ``speech_bounds`` gives the speech span, or is "detect": the ITU-T P.56 activity meter then finds it);
 pitch comes from ``f0=``: a frame-level track, or ``"track"`` for the device pitch tracker (pitch.py: Praat's autocorrelation
 method restated from its publication, parity with Praat unpinned and therefore opt-in; ``track_pitch=True`` makes it the default of
 this instance); with neither, pitch is None and the acoustic model predicts it from the cloned durations.
@@ -46,6 +46,7 @@ class UtteranceCloner:
 
     def extract_prosody_batch(self, transcripts, waves, sr, f0=None, speech_bounds=None, on_line_fine_tune=True, dropout_masks=None):
         """Per utterance (durations, pitch or None, energy, start_silence, end_silence) for phoneme transcripts and recordings at `sr`.
+        speech_bounds: None, per utterance a (start, end) pair or "detect", or "detect" for all (align.extract_prosody_batch).
         dropout_masks (fine_tune_aligner instances): per utterance [5 steps][5 layers] boolean [T, 512] keep-masks in place of the
         ones drawn from fine_tune_seed."""
         fine_tune = None
@@ -89,7 +90,9 @@ class UtteranceCloner:
             return utt
         data, sr = style.read_audio(path_to_reference_audio_for_intonation)
         ref16 = style.normalize_reference_audio(data, sr)
-        if speech_bounds is not None:
+        if isinstance(speech_bounds, str):  # "detect": the span that was found is what the silences leave
+            ref16 = ref16[sil_start:len(ref16) - sil_end]
+        elif speech_bounds is not None:
             ref16 = ref16[int(speech_bounds[0]):int(speech_bounds[1])]
         report = self.tts._comparator().compare([cloned.reshape(-1).float().cpu().numpy()], [ref16], self.tts.SAMPLE_RATE, style.SR)[0]
         return utt, report

@@ -14,7 +14,8 @@ script written against the reference (run_text_to_file_reader.py:8-16) works unc
   each scale did), ``prosody_curves=`` / ``curves=`` (per-phoneme prosody curves: stress one word, prosody.emphasis),
   ``evaluate_against_recordings`` (synthesise and measure against recordings of the same sentences: MCD along a DTW path and
   the F0 errors, compare.py), ``loudness=`` / ``peak_ceiling=`` (every utterance brought to a target integrated loudness after
-  ITU-R BS.1770 under a sample-peak ceiling, on the device: loudness.py)
+  ITU-R BS.1770 under a sample-peak ceiling, on the device: loudness.py), ``speech_level=`` (the same for the active
+  speech level after ITU-T P.56: activity.py), ``trim_silence=`` on ``set_utterance_embedding``
 
 * ``set_utterance_embedding(path)`` (:103-114): reference audio -> log-mel -> GST style embedding on the GPU (style.py)
 
@@ -22,6 +23,7 @@ What is NOT here (unavailable offline): grapheme-to-phon
 raises - pass phoneme strings with ``input_is_phones=True``) and the silero voice-activity trim of the reference audio.
 """
 import os
+import warnings
 import wave as _wave
 
 import numpy as np
@@ -164,6 +166,7 @@ class ToucanTTSInterface(torch.nn.Module):
         self.last_prosody_stats = None  # (before, after) of the last batch that took per-utterance prosody scales or curves
         self.last_prosody_span_stats = None  # per utterance (before, after) of its Spans, of the last batch that took prosody curves
         self.last_loudness = None  # float64 [B, 8] on the device (loudness.LOUDNESS_COLUMNS) of the last call that took loudness=
+        self.last_speech_activity = None  # (stats [B, 8], runs [B, 64, 2], counts [B, 16]) on the device of the last call that took speech_level=
 
 
         self.default_utterance_embedding = checkpoint["default_emb"].to(self.device)
@@ -171,7 +174,12 @@ class ToucanTTSInterface(torch.nn.Module):
         self.eval()
 
     # ---- setters (:103-130) -------------------------------------------------------------------------
-    def set_utterance_embedding(self, path_to_reference_audio="", embedding=None):
+    _warned_trim = False
+
+    def set_utterance_embedding(self, path_to_reference_audio="", embedding=None, trim_silence=False):
+        """``trim_silence`` (additive; the reference's ``cut_silence=True`` uses silero, which is not reproduced): cut the normalised
+        16 kHz wave to the bounds of the speech that the ITU-T P.56 activity meter finds (activity.py, 30 ms lead) before the
+        log-mel.  If it finds none, or fewer than 513 samples are left, the wave stays uncut, with one warning."""
         if embedding is not None:
             self.default_utterance_embedding = embedding.squeeze().to(self.device)
             return
@@ -184,7 +192,17 @@ class ToucanTTSInterface(torch.nn.Module):
             self._style = (style.LogMel(self.device), style.StyleEngine(_to_numpy_sd(_load_checkpoint(path)["style_emb_func"]), self.device))
         data, sr = style.read_audio(path_to_reference_audio)
         logmel, gst = self._style
-        spec = logmel.forward(style.normalize_reference_audio(data, sr))
+        wave16 = style.normalize_reference_audio(data, sr)
+        if trim_silence:
+            from . import activity
+            packed = torch.from_numpy(np.asarray(wave16, dtype=np.float32).reshape(-1)).to(self.device)
+            found = activity.bounds(self._activity().measure(packed, [(0, packed.numel())], style.SR), lead=style.SR * activity.DEFAULT_LEAD_MS // 1000)[0]
+            if found is not None and found[1] - found[0] >= 513:
+                wave16 = wave16[found[0]:found[1]]
+            elif not ToucanTTSInterface._warned_trim:
+                ToucanTTSInterface._warned_trim = True
+                warnings.warn("trim_silence=True: no speech of at least 513 samples was found in the reference audio; it is used uncut")
+        spec = logmel.forward(wave16)
         self.default_utterance_embedding = gst.forward([spec])[0].to(self.device)
 
     def set_language(self, lang_id):
@@ -218,16 +236,18 @@ class ToucanTTSInterface(torch.nn.Module):
                 pcm16=False,
                 prosody_curves=None,
                 loudness=None,
-                peak_ceiling=-1.0):
+                peak_ceiling=-1.0,
+                speech_level=None):
         """The reference's signature (ToucanTTSInterface.py:132-143) plus additive keywords.  ``z_noise`` [80, T]: the PostFlow
         noise 0.8 N(0,1) the reference draws inside the model (Glow.py:363), so that a call can be reproduced and checked
         against the oracle; None draws it on the device.  ``sample_rate`` / ``pcm16``: the waveform at another rate than 24 kHz
         and / or as int16, converted on the device (resample.py); the figure of ``view`` keeps drawing the 24 kHz wave.
         ``prosody_curves``: this utterance's per-phoneme curves, an [L, 5] array or a list of ``prosody.Span`` (as one entry of
         ``synthesize_batch``'s keyword, documented there); None is the call as it was.  ``loudness`` / ``peak_ceiling``: as in
-        ``synthesize_batch``; the figure of ``view`` then draws the normalised 24 kHz wave."""
+        ``synthesize_batch``; the figure of ``view`` then draws the normalised 24 kHz wave.  ``speech_level``: as in ``synthesize_batch``."""
         self._check_output_format(sample_rate, pcm16)
         self._check_loudness(loudness, peak_ceiling)
+        self._check_speech_level(loudness, speech_level, peak_ceiling)
         with torch.inference_mode():
             phones = self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
             curves = {} if prosody_curves is None else dict(prosody_curves=[prosody_curves])
@@ -239,7 +259,7 @@ class ToucanTTSInterface(torch.nn.Module):
                                                    duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
                                                    energy_variance_scale=energy_variance_scale,
                                                    pause_duration_scaling_factor=pause_duration_scaling_factor, **curves)
-            wav24 = self._normalize(wav24, spans, loudness, peak_ceiling)
+            wav24 = self._normalize(wav24, spans, loudness, peak_ceiling, speech_level)
             wav, out_spans = self._convert(wav24, spans, sample_rate, pcm16)
             wavs = [wav[b:b + n] for b, n in out_spans]
         if view or return_plot_as_filepath:  # ToucanTTSInterface.py:171-226 (matplotlib only: plotting.py)
@@ -275,9 +295,9 @@ class ToucanTTSInterface(torch.nn.Module):
         self.last_prosody_span_stats = out.get("prosody_span_stats")
         return wav, list(zip(rag.begins, rag.lengths))
 
-    def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, **kw):
+    def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None, **kw):
         wav, spans = self._synthesize_packed(phones, embs, langs, z_noise=z_noise, **kw)
-        wav = self._normalize(wav, spans, loudness, peak_ceiling)
+        wav = self._normalize(wav, spans, loudness, peak_ceiling, speech_level)
         wav, spans = self._convert(wav, spans, sample_rate, pcm16)
         return [wav[b:b + n] for b, n in spans]
 
@@ -321,10 +341,34 @@ class ToucanTTSInterface(torch.nn.Module):
             self._meter_obj = ld.LoudnessMeter(self.device)
         return self._meter_obj
 
-    def _normalize(self, wav, spans, loudness, peak_ceiling):
-        """The packed 24 kHz waveform with every utterance at ``loudness`` LUFS (ITU-R BS.1770 integrated loudness) or as close
-        as the sample-peak ceiling ``peak_ceiling`` dBFS allows, measured and scaled on the device behind the vocoder on its
-        stream; ``self.last_loudness`` gets the statistics.  None returns the waveform as it came, without a launch."""
+    @staticmethod
+    def _check_speech_level(loudness, speech_level, peak_ceiling):
+        """ValueError for ``loudness`` and ``speech_level`` together, for a target or a ceiling that is not finite, or a ceiling
+        above 0 dBFS; True if the waveform is to be brought to an active speech level at all (``speech_level`` is not None)."""
+        if speech_level is None:
+            return False
+        if loudness is not None:
+            raise ValueError("loudness and speech_level are two normalisations of the same waveform: give one of them")
+        from . import activity as ac
+        ac.check_target(speech_level, peak_ceiling)
+        return True
+
+    def _activity(self):
+        if getattr(self, "_activity_obj", None) is None:
+            from . import activity as ac
+            self._activity_obj = ac.SpeechActivity(self.device)
+        return self._activity_obj
+
+    def _normalize(self, wav, spans, loudness, peak_ceiling, speech_level=None):
+        """The packed 24 kHz waveform with every utterance at ``loudness`` LUFS (ITU-R BS.1770 integrated loudness) or at the
+        active speech level ``speech_level`` dB (ITU-T P.56), or as close as the sample-peak ceiling ``peak_ceiling`` dBFS allows,
+        measured and scaled on the device behind the vocoder on its stream; ``self.last_loudness`` or
+        ``self.last_speech_activity`` gets the statistics.  Both None returns the waveform as it came, without a launch."""
+        if self._check_speech_level(loudness, speech_level, peak_ceiling):
+            meter = self._activity()
+            wav, stats = meter.normalize(wav.contiguous(), spans, self.SAMPLE_RATE, speech_level, peak_ceiling)
+            self.last_speech_activity = (stats, meter.last_runs, meter.last_counts)
+            return wav
         if not self._check_loudness(loudness, peak_ceiling):
             return wav
         wav, self.last_loudness = self._meter().normalize(wav.contiguous(), spans, self.SAMPLE_RATE, loudness, peak_ceiling)
@@ -339,7 +383,7 @@ class ToucanTTSInterface(torch.nn.Module):
     def synthesize_batch(self, texts, input_is_phones=True, utterance_embeddings=None, z_noise=None, durations=None, pitch=None,
                          energy=None, duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
                          pause_duration_scaling_factor=1.0, distributed=False, sample_rate=None, pcm16=False, prosody_curves=None,
-                         loudness=None, peak_ceiling=-1.0):
+                         loudness=None, peak_ceiling=-1.0, speech_level=None):
         """Additive API: a ragged batch in one pass; each utterance equals the reference run on it alone (16-bit configurations: bit
         for bit whatever the batch; fp32: durations / pitch / energy bit for bit, the mel to fp32 rounding order - DESIGN.md section 4).
         texts: phoneme strings (or [L,62] feature tensors).  durations / pitch / energy: optional per-utterance gold prosody (the
@@ -372,10 +416,21 @@ class ToucanTTSInterface(torch.nn.Module):
         not an oversampled true peak.  An utterance without a loudness (shorter than 400 ms, or silent) keeps its bits.
         ``self.last_loudness``: float64 [B, 8] on the device, columns ``loudness.LOUDNESS_COLUMNS`` (the loudness found, the peak,
         the blocks and what each gate kept, the loudest block, the gain applied, the loudness reached).  ValueError for a target or
-        ceiling that is not finite, a ceiling above 0, and with ``distributed=True``."""
+        ceiling that is not finite, a ceiling above 0, and with ``distributed=True``.
+        ``speech_level``: None (the call as it was) or a target active speech level in dB re full scale, e.g. -26 (the convention
+        of listening tests).  Every utterance's active speech level after ITU-T P.56 method B (activity.py, DESIGN.md section 18;
+        agreement with the ITU's sv56 is unpinned) is measured at 24 kHz on the device and the utterance scaled to the target, in
+        the same place and under the same ``peak_ceiling`` as ``loudness``; an utterance without a level keeps its bits.
+        ``self.last_speech_activity`` = (stats float64 [B, 8], columns ``activity.ACTIVITY_COLUMNS``: both levels, the activity
+        factor, the threshold, the bounds of the speech in samples, the gain, the level reached; runs int64 [B, 64, 2]: the runs of
+        speech, ``activity.pauses`` gives the pauses between them; counts int64 [B, 16]: the active samples per threshold and the
+        number of runs), all on the device.  ValueError together with ``loudness`` and wherever ``loudness`` raises one."""
         if distributed and loudness is not None:
             raise ValueError("loudness is not available with distributed=True: the sharded exchange carries the waveforms as synthesised")
+        if distributed and speech_level is not None:
+            raise ValueError("speech_level is not available with distributed=True: the sharded exchange carries the waveforms as synthesised")
         self._check_loudness(loudness, peak_ceiling)
+        self._check_speech_level(loudness, speech_level, peak_ceiling)
         if distributed and (sample_rate is not None or pcm16):
             raise ValueError("sample_rate / pcm16 are not available with distributed=True: the sharded exchange carries 24 kHz float32")
         self._check_output_format(sample_rate, pcm16)
@@ -395,7 +450,8 @@ class ToucanTTSInterface(torch.nn.Module):
                 kw["prosody_curves"] = prosody_curves
             with torch.inference_mode():
                 return self._synthesize(feats, embs, [self._lang()] * len(feats), z_noise=z_noise, durations=durations, pitch=pitch,
-                                        energy=energy, sample_rate=sample_rate, pcm16=pcm16, loudness=loudness, peak_ceiling=peak_ceiling, **kw)
+                                        energy=energy, sample_rate=sample_rate, pcm16=pcm16, loudness=loudness, peak_ceiling=peak_ceiling,
+                                        speech_level=speech_level, **kw)
         from . import distributed as dd
         return dd.synthesize_sharded(self, feats, embs, z_noise, durations, pitch, energy, kw)
 
@@ -413,7 +469,7 @@ class ToucanTTSInterface(torch.nn.Module):
         (style.read_audio) or a (wave, sample rate) tuple; several channels are averaged.  f0: as ``compare`` takes it.  -> one dict
         per text; with ``keep_waves`` it also holds "synth" (float32, 24 kHz), "recording" (mono, float32) and "recording_sr", the two
         waves that were compared.  ValueError for lists of unequal length, for ``distributed=True`` and for ``sample_rate`` /
-        ``pcm16`` (the comparison takes the 24 kHz float waveform), for ``loudness`` (both waves are divided by their peaks anyway), and
+        ``pcm16`` (the comparison takes the 24 kHz float waveform), for ``loudness`` and ``speech_level`` (both waves are divided by their peaks anyway), and
         what ``compare`` refuses."""
         if synthesis_keywords.get("distributed"):
             raise ValueError("evaluate_against_recordings is not available with distributed=True: the comparison runs on one device")
@@ -421,6 +477,8 @@ class ToucanTTSInterface(torch.nn.Module):
             raise ValueError("evaluate_against_recordings compares the 24 kHz float waveform: sample_rate / pcm16 do not apply")
         if synthesis_keywords.get("loudness") is not None:
             raise ValueError("evaluate_against_recordings divides both waves by their peaks before it compares them: loudness does not apply")
+        if synthesis_keywords.get("speech_level") is not None:
+            raise ValueError("evaluate_against_recordings divides both waves by their peaks before it compares them: speech_level does not apply")
         if len(texts) != len(recordings):
             raise ValueError(f"{len(texts)} texts for {len(recordings)} recordings")
         from . import style
@@ -438,13 +496,14 @@ class ToucanTTSInterface(torch.nn.Module):
         return results
 
     def synthesize_ensemble(self, text, utterance_embeddings, durations=None, pitch=None, energy=None, input_is_phones=True, z_noise=None,
-                            sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0):
+                            sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None):
         """Several voices speaking one text with the same prosody, averaged (UtteranceCloner.py:166-194's ensemble) - as ONE batch
         over the voices instead of a loop that swaps the default embedding.  Without gold durations the voices may predict
         different lengths; the mean is then taken over the common prefix.  ``sample_rate`` / ``pcm16`` convert the 24 kHz mean;
-        ``loudness`` / ``peak_ceiling`` (as in ``synthesize_batch``) normalise the mean, before that conversion."""
+        ``loudness`` / ``peak_ceiling`` or ``speech_level`` (as in ``synthesize_batch``) normalise the mean, before that conversion."""
         convert = self._check_output_format(sample_rate, pcm16)
         self._check_loudness(loudness, peak_ceiling)
+        self._check_speech_level(loudness, speech_level, peak_ceiling)
         n = len(utterance_embeddings)
         rep = lambda v: None if v is None else [v] * n
         waves = self.synthesize_batch([text] * n, input_is_phones=input_is_phones, utterance_embeddings=list(utterance_embeddings),
@@ -452,7 +511,7 @@ class ToucanTTSInterface(torch.nn.Module):
         m = min(w.numel() for w in waves)
         mean = torch.stack([w[:m] for w in waves]).mean(dim=0)
         with torch.inference_mode():
-            mean = self._normalize(mean, [(0, m)], loudness, peak_ceiling)
+            mean = self._normalize(mean, [(0, m)], loudness, peak_ceiling, speech_level)
         if not convert:
             return mean
         wav, spans = self._convert(mean, [(0, m)], sample_rate, pcm16)
@@ -460,7 +519,8 @@ class ToucanTTSInterface(torch.nn.Module):
 
     def synthesize_grid(self, text, duration_scaling_factors=(1.0,), pitch_variance_scales=(1.0,), energy_variance_scales=(1.0,),
                         pause_duration_scaling_factors=(1.0,), input_is_phones=True, utterance_embedding=None, durations=None, pitch=None,
-                        energy=None, z_noise=None, sample_rate=None, pcm16=False, curves=None, loudness=None, peak_ceiling=-1.0):
+                        energy=None, z_noise=None, sample_rate=None, pcm16=False, curves=None, loudness=None, peak_ceiling=-1.0,
+                        speech_level=None):
         """Additive API: ONE text (a phoneme string, or its [L, 62] feature tensor) at every combination of the four tuples of prosody scales - the Cartesian product in row-major
         order of the tuples as listed (the pause factor varies fastest) - synthesised as ragged batches of at most MAX_FILE_BATCH
         variants with per-utterance scales instead of one pass per setting.  Returns one dict per variant, in that order:
@@ -477,10 +537,14 @@ class ToucanTTSInterface(torch.nn.Module):
         frames it occupies.  ``curves=[prosody.emphasis(feats, [k]) for k in range(len(prosody.word_spans(feats)))]`` is the emphasis
         sweep over the words of a sentence in one call.
         ``loudness`` / ``peak_ceiling`` (as in ``synthesize_batch``): every variant is normalised on its own and its dict gains
-        ``loudness``, its float64 [8] row of statistics on the device; ``self.last_loudness`` holds all rows, in variant order."""
+        ``loudness``, its float64 [8] row of statistics on the device; ``self.last_loudness`` holds all rows, in variant order.
+        ``speech_level`` (as in ``synthesize_batch``) likewise: every dict gains ``speech_activity`` = (its stats row [8], its runs
+        [64, 2], its counts [16]) - what ``pause_duration_scaling_factor`` really did to the pauses can be read from the runs
+        (``activity.pauses``) - and ``self.last_speech_activity`` holds all rows, in variant order."""
         self._check_output_format(sample_rate, pcm16)
         normalise = self._check_loudness(loudness, peak_ceiling)
-        rows = []
+        level = self._check_speech_level(loudness, speech_level, peak_ceiling)
+        rows, activity_rows = [], []
         variants = prosody.grid(duration_scaling_factors, pitch_variance_scales, energy_variance_scales, pause_duration_scaling_factors)
         which = [None] * len(variants)  # the curve alternative of every variant
         if curves is not None:
@@ -507,33 +571,41 @@ class ToucanTTSInterface(torch.nn.Module):
                                                          durations=rep(durations), pitch=rep(pitch), energy=rep(energy),
                                                          **{name: [v[k] for v in chunk] for k, name in enumerate(prosody.KNOBS)}, **kw)
                 before, after = self.last_prosody_stats
-                wav24 = self._normalize(wav24, spans24, loudness, peak_ceiling)
+                wav24 = self._normalize(wav24, spans24, loudness, peak_ceiling, speech_level)
                 if normalise:
                     rows.append(self.last_loudness)
+                if level:
+                    activity_rows.append(self.last_speech_activity)
                 wav, spans = self._convert(wav24, spans24, sample_rate, pcm16)
                 for i, scales in enumerate(chunk):
                     results.append({"scales": scales, "wave": wav[spans[i][0]:spans[i][0] + spans[i][1]], "frames": int(spans24[i][1]) // 384,
                                     "stats_before": before[i], "stats_after": after[i]})
                     if normalise:
                         results[-1]["loudness"] = rows[-1][i]
+                    if level:
+                        results[-1]["speech_activity"] = tuple(t[i] for t in activity_rows[-1])
                     if curves is not None:  # (a chunk whose alternatives are all None took the path without curves: no Spans, no blocks)
                         none = np.zeros((0, len(prosody.STATS)), dtype=np.float32)
                         per = self.last_prosody_span_stats
                         results[-1].update(curve=which[lo + i], span_stats=(none, none) if per is None else per[i])
             if normalise:
                 self.last_loudness = torch.cat(rows)
+            if level:
+                self.last_speech_activity = tuple(torch.cat([r[k] for r in activity_rows]) for k in range(3))
         return results
 
     def stream(self, text, input_is_phones=False, chunk_frames=512, halo_frames=None, max_batch=4, z_noise=None, sample_rate=None, pcm16=False, loudness=None,
-               peak_ceiling=-1.0, **prosody):
+               peak_ceiling=-1.0, speech_level=None, **prosody):
         """Generator of waveform pieces for ONE (long) text: the acoustic model runs once, the vocoder chunk-wise with overlap
         (streaming.py) - the concatenation equals ``self(text, ...)`` bit for bit, the first piece is ready after one chunk and the
         vocoder's workspace is bounded by ``max_batch`` chunks.  prosody: the keyword arguments of ``forward`` (gold durations /
         pitch / energy, scaling factors, ``prosody_curves``).  ``sample_rate`` / ``pcm16``: the pieces at another rate and / or as int16, converted as
         they come (resample.Resampler.streamer); their concatenation equals ``self(text, sample_rate=..., pcm16=...)`` bit for bit.
-        ``loudness`` raises ValueError: the integrated loudness is a property of the whole utterance, which a stream does not have."""
+        ``loudness`` and ``speech_level`` raise ValueError: both are properties of the whole utterance, which a stream does not have."""
         if loudness is not None:
             raise ValueError("stream() cannot normalise loudness: the integrated loudness needs the whole utterance; use forward(loudness=...)")
+        if speech_level is not None:
+            raise ValueError("stream() cannot normalise the speech level: the active speech level needs the whole utterance; use forward(speech_level=...)")
         from . import streaming
         convert = self._check_output_format(sample_rate, pcm16)
         halo = streaming.DEFAULT_HALO if halo_frames is None else halo_frames
@@ -583,7 +655,8 @@ class ToucanTTSInterface(torch.nn.Module):
                      sample_rate=None,
                      pcm16=False,
                      loudness=None,
-                     peak_ceiling=-1.0):
+                     peak_ceiling=-1.0,
+                     speech_level=None):
         """Same result as the reference's sentence loop (:231-285: silence, sentence, silence, ... with blank strings skipped,
         24 kHz float file or sample-doubled 48 kHz PCM16), but the sentences go through the engines as ragged batches of up to
         MAX_FILE_BATCH utterances and the file is assembled once on the host.  ``sample_rate`` / ``pcm16`` (additive): every
@@ -592,10 +665,16 @@ class ToucanTTSInterface(torch.nn.Module):
         reference's doubling.  ``loudness`` / ``peak_ceiling`` (additive, as in ``synthesize_batch``): every sentence is normalised on
         its own (a measurement of the whole file gates the silences out, but not the blocks that straddle the edge of a sentence: it
         reads a little below the sentences);
-        ``self.last_loudness`` holds the rows of the spoken sentences in file order.  Not with ``increased_compatibility_mode``."""
+        ``self.last_loudness`` holds the rows of the spoken sentences in file order.  Not with ``increased_compatibility_mode``.
+        ``speech_level`` (additive, as in ``synthesize_batch``) likewise: every sentence on its own, ``self.last_speech_activity``
+        holds the rows of the spoken sentences in file order; not with ``increased_compatibility_mode``."""
         if increased_compatibility_mode and loudness is not None:
             raise ValueError("increased_compatibility_mode is the reference's path as it is: it does not combine with loudness")
+        if increased_compatibility_mode and speech_level is not None:
+            raise ValueError("increased_compatibility_mode is the reference's path as it is: it does not combine with speech_level")
         normalise = self._check_loudness(loudness, peak_ceiling)
+        level = self._check_speech_level(loudness, speech_level, peak_ceiling)
+        activity_rows = {}
         if increased_compatibility_mode and (sample_rate is not None or pcm16):
             raise ValueError("increased_compatibility_mode is the reference's sample doubling to 48 kHz PCM16: it does not combine with "
                              "sample_rate / pcm16")
@@ -622,13 +701,19 @@ class ToucanTTSInterface(torch.nn.Module):
                                               energy=[enes[i] for i in idx] if has_e else None,
                                               duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
                                               energy_variance_scale=energy_variance_scale, sample_rate=sample_rate, pcm16=pcm16,
-                                              loudness=loudness, peak_ceiling=peak_ceiling)
+                                              loudness=loudness, peak_ceiling=peak_ceiling, speech_level=speech_level)
                 for r, (i, w) in enumerate(zip(idx, waves)):
                     pieces[i] = w.cpu().numpy()
                     if normalise:
                         rows[i] = self.last_loudness[r]
+                    if level:
+                        activity_rows[i] = tuple(t[r] for t in self.last_speech_activity)
         if normalise:
             self.last_loudness = torch.stack([rows[i] for i in spoken]) if spoken else torch.zeros((0, 8), dtype=torch.float64, device=self.device)
+        if level:
+            empty = (torch.zeros((0, 8), dtype=torch.float64, device=self.device), torch.zeros((0, 64, 2), dtype=torch.int64, device=self.device),
+                     torch.zeros((0, 16), dtype=torch.int64, device=self.device))
+            self.last_speech_activity = tuple(torch.stack([activity_rows[i][k] for i in spoken]) for k in range(3)) if spoken else empty
         rate = self.SAMPLE_RATE if sample_rate is None else int(sample_rate)
         gap = self.SILENCE_SAMPLES
         if rate != self.SAMPLE_RATE:
