@@ -16,8 +16,8 @@ import math
 import numpy as np
 import torch
 
-from . import capi
-from .loudness import segment_samples
+from . import capi, segments
+from .segments import SegmentMeter, segment_samples
 
 ACTIVITY_COLUMNS = ("active_db", "long_term_db", "activity", "threshold_db", "speech_begin", "speech_end", "gain", "active_db_after")
 MIN_RATE, MAX_RATE = capi.ACTIVITY_MIN_RATE, capi.ACTIVITY_MAX_RATE
@@ -50,11 +50,7 @@ def kernel_table(sr):
 
 
 def check_target(target_db, peak_ceiling_dbfs):
-    for name, v in (("target", target_db), ("peak ceiling", peak_ceiling_dbfs)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-            raise ValueError(f"the speech level {name} must be a finite number, not {v!r}")
-    if peak_ceiling_dbfs > 0:
-        raise ValueError(f"the peak ceiling {peak_ceiling_dbfs!r} dBFS is above full scale (0 dBFS)")
+    segments.check_target("speech level", target_db, peak_ceiling_dbfs)
 
 
 def bounds(stats, lead):
@@ -81,33 +77,15 @@ def pauses(runs, count):
     return [(int(rows[i][1]), int(rows[i + 1][0])) for i in range(len(rows) - 1)]
 
 
-class SpeechActivity:
+class SpeechActivity(SegmentMeter):
     """``measure(packed_wave, spans, sr)`` and ``normalize(packed_wave, spans, sr, target_db, peak_ceiling_dbfs)`` for a ragged
     batch on the device.  The tables (g, h and T) are uploaded once per rate and kept.  Of the last call: ``last_counts`` int64
     [B, 16] (a_0 .. a_14, the number of runs), ``last_runs`` int64 [B, max_runs, 2] (rows past the count hold 0), ``last_sums``
     float64 [B, 2] (sum of x^2, max |x|), ``last_states`` float64 [B, most segments, 2] (p, q at every segment's start)."""
 
     def __init__(self, device):
-        self.lib = capi.lib()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise capi.ToucanHipError(f"device {str(self.device)!r}: the speech-activity meter runs on the GPU only")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.tile_segments = int(self.lib.tts_activity_tile_segments())
-        self._tables = {}
+        super().__init__(device, "speech-activity meter", kernel_table, "tts_activity_tile_segments")
         self.last_counts = self.last_runs = self.last_sums = self.last_states = None
-
-    def table(self, sr):
-        if int(sr) not in self._tables:
-            self._tables[int(sr)] = torch.from_numpy(kernel_table(sr)).to(self.device)
-        return self._tables[int(sr)]
-
-    def _rows(self, wave, spans):
-        assert wave.dtype == torch.float32 and wave.dim() == 1 and wave.device == self.device and wave.is_contiguous()
-        rows = np.ascontiguousarray(np.asarray([(int(b), int(n)) for b, n in spans], dtype=np.int64).reshape(-1, 2))
-        # from pinned memory, so that the copy queues behind the work already on the stream instead of waiting for it
-        return rows, torch.from_numpy(rows).pin_memory().to(self.device, non_blocking=True)
 
     def _measure(self, wave, rows, rows_d, sr, target, ceiling, max_runs, level_only=False):
         """The five passes on the current stream -> stats [B, 8] float64 on the device.  ``level_only``: passes 1 to 4 alone, and
@@ -117,7 +95,7 @@ class SpeechActivity:
             raise ValueError(f"max_runs {max_runs} is negative")
         dev = self.device
         stats = torch.empty((B, len(ACTIVITY_COLUMNS)), dtype=torch.float64, device=dev)
-        max_segments = max(1, int(-(-rows[:, 1].max() // S))) if B else 1
+        max_segments = self._max_segments(rows, S)
         counts = torch.zeros((B, capi.ACTIVITY_COUNTS), dtype=torch.int64, device=dev)
         runs = torch.zeros((B, max_runs, 2), dtype=torch.int64, device=dev)
         sums = torch.zeros((B, 2), dtype=torch.float64, device=dev)
@@ -167,15 +145,8 @@ class SpeechActivity:
         check_target(target_db, peak_ceiling_dbfs)
         rows, rows_d = self._rows(packed_wave, spans)
         stats = self._measure(packed_wave, rows, rows_d, sr, target_db, peak_ceiling_dbfs, max_runs)
-        if out is None:
-            tiled = len(rows) > 0 and int(rows[0, 0]) == 0 and int(rows[-1].sum()) == packed_wave.numel() and \
-                bool((rows[1:, 0] == rows[:-1].sum(axis=1)).all())
-            out = torch.empty_like(packed_wave) if tiled else packed_wave.clone()
-        assert out.dtype == torch.float32 and out.shape == packed_wave.shape and out.device == self.device and out.is_contiguous()
+        out = self._apply_gain(packed_wave, rows, rows_d, stats, out)
         if len(rows):
-            capi.check(self.lib.tts_apply_gain(packed_wave.data_ptr(), packed_wave.numel(), rows_d.data_ptr(), rows.ctypes.data, len(rows),
-                                               int(rows[:, 1].max()), stats.data_ptr(), out.data_ptr(),
-                                               torch.cuda.current_stream(self.device).cuda_stream), "tts_apply_gain")
             again = self._measure(out, rows, rows_d, sr, float("nan"), 0.0, 0, level_only=True)
             stats[:, ACTIVITY_COLUMNS.index("active_db_after")] = again[:, 0]
         return out, stats

@@ -7,11 +7,9 @@
 //   tts_activity_runs           pass 5: the envelope against the final threshold, then runs and bounds: two launches
 //   tts_activity_tile_segments  segments per workgroup
 //
-// The envelope (p, q) is a linear recurrence over the samples, so the layout is the loudness meter's (loudness.hip): the state at
-// the end of a segment is T (state at its start) + (end state of the segment run from zero).  Pass 1 runs every segment from zero,
-// one lane per segment; pass 2 carries the states along each utterance; pass 3 runs every segment again from its true state.  A
-// workgroup (one wavefront) stages [AC_SEGS segments] x [AC_T samples] through LDS, rows AC_T + 1 dwords apart, and issues the
-// next chunk's loads before it works through the current one.
+// The envelope (p, q) is a linear recurrence over the samples: passes 1 to 3 over 100 ms segments, the LDS staging and the carry
+// of the states (transition T) are segment_scan.h's, and pass 5 walks the segments the same way.  This file holds the envelope's
+// step, the ladder, the level and the runs.
 //
 // The hangover needs no pass over the samples: a segment is no longer than the hangover, so every gap inside it is bridged and
 // its first and last sample at a threshold say how many of its samples are active, given the hangover left at its start.  The
@@ -19,29 +17,13 @@
 //
 // Batch independence: a segment's chain is the same instructions on the same values whichever lane, workgroup or batch holds it;
 // passes 2, 4 and the walk of pass 5 go in index order per utterance.
-#include <math.h>
-
-#include "common.h"
+#include "segment_scan.h"
 #include "../../include/toucan_activity.h"
 
 namespace tts {
 
-constexpr int AC_SEGS = 64;             // segments per workgroup = lanes
-constexpr int AC_T = 64;                // samples of every segment staged at a time
-constexpr int AC_STRIDE = AC_T + 1;     // dwords between the rows of a tile
 constexpr int AC_J = TTS_ACTIVITY_THRESHOLDS;
-constexpr int AC_POS = 32;              // int32 per slot in pos: 16 (first, last) pairs
-
-struct ActSpan {
-  int64_t begin, count;
-};
-
-// a row that does not lie inside the wave counts as an utterance of no samples
-__device__ __forceinline__ ActSpan act_span(const int64_t* __restrict__ spans, int u, int64_t n_samples) {
-  ActSpan s = {spans[2 * u], spans[2 * u + 1]};
-  if (s.begin < 0 || s.count < 0 || s.begin > n_samples || s.count > n_samples - s.begin) s.count = 0;
-  return s;
-}
+constexpr int AC_POS = 32;  // int32 per slot in pos: 16 (first, last) pairs
 
 // how many thresholds of the ladder q meets: c_j = 2^(j - 15) <= q exactly for j <= (unbiased exponent of q) + 15
 __device__ __forceinline__ int ladder_level(double q) {
@@ -54,16 +36,16 @@ enum { AC_ZERO = 0, AC_LADDER = 1, AC_FINAL = 2 };
 // AC_ZERO: pass 1, from the zero state, end state -> state[u][k] of every complete segment.  AC_LADDER: pass 3, from state[u][k],
 // sq, peak and the positions at the 15 thresholds.  AC_FINAL: pass 5, from state[u][k], the positions at c* -> entry 15 of pos.
 template <int MODE>
-__global__ __launch_bounds__(AC_SEGS) void envelope_kernel(const float* __restrict__ x, int64_t n_samples, const int64_t* __restrict__ spans,
-                                                           int S, const double* __restrict__ table, int64_t max_segments,
-                                                           double* __restrict__ state, double* __restrict__ sq, float* __restrict__ peak,
-                                                           int32_t* __restrict__ pos, const double* __restrict__ stats) {
-  __shared__ float tile[2][AC_SEGS * AC_STRIDE];
+__global__ __launch_bounds__(SEG_LANES) void envelope_kernel(const float* __restrict__ x, int64_t n_samples, const int64_t* __restrict__ spans,
+                                                             int S, const double* __restrict__ table, int64_t max_segments,
+                                                             double* __restrict__ state, double* __restrict__ sq, float* __restrict__ peak,
+                                                             int32_t* __restrict__ pos, const double* __restrict__ stats) {
+  __shared__ float tile[2][SEG_TILE];
   const int u = blockIdx.y, lane = threadIdx.x;
-  const ActSpan sp = act_span(spans, u, n_samples);
+  const WaveSpan sp = load_span(spans, u, n_samples);
   const int64_t n_full = sp.count / S;
   const int64_t n_slots = (sp.count + S - 1) / S;
-  const int64_t k0 = (int64_t)blockIdx.x * AC_SEGS;
+  const int64_t k0 = (int64_t)blockIdx.x * SEG_LANES;
   if (k0 >= (MODE == AC_ZERO ? n_full : n_slots)) return;  // the whole workgroup: before any barrier
   const int64_t k = k0 + lane;
   const float* base = x + sp.begin + k0 * S;
@@ -91,58 +73,27 @@ __global__ __launch_bounds__(AC_SEGS) void envelope_kernel(const float* __restri
   for (int j = 0; j < AC_J; ++j) first[j] = last[j] = -1;
   int first_c = -1, last_c = -1;
 
-  const int chunks = (S + AC_T - 1) / AC_T;
-  float next[AC_SEGS];
-  // chunk c of row r: samples r S + c AC_T + (0 .. AC_T - 1) from `base`.  fetch() issues all 64 loads, each at an index clamped
-  // into the utterance, with 32-bit offsets from the uniform base (a tile spans at most 64 * 19 200 + 64 samples), and uses none
-  // of them; park() writes them to LDS, 0 for what lies past the segment or the utterance.
-  const int lim = (int)min(avail, (int64_t)0x7fffffff);
-  auto fetch = [&](int c) {
-    const int t = c * AC_T + lane;
+  walk_segments(tile, base, avail, S, lane, [&](int ts, float xf) {
+    const double ax = (double)fabsf(xf);
+    p = fma(g, p, h * ax);
+    q = fma(g, q, h * p);
+    if constexpr (MODE == AC_LADDER) {
+      e = fma(ax, ax, e);
+      pk = fmaxf(pk, fabsf(xf));
+      const int L = ts < Sk ? ladder_level(q) : 0;  // the zeros behind a partial slot are not samples
 #pragma unroll
-    for (int r = 0; r < AC_SEGS; ++r) next[r] = base[min(r * S + t, lim - 1)];
-  };
-  auto park = [&](int c) {
-    const int t = c * AC_T + lane;
-    const bool in_segment = t < S;
-    float* col = &tile[c & 1][lane];
-#pragma unroll
-    for (int r = 0; r < AC_SEGS; ++r) col[r * AC_STRIDE] = (in_segment && r * S + t < lim) ? next[r] : 0.0f;
-  };
-  fetch(0);
-  park(0);
-  __syncthreads();
-  for (int c = 0; c < chunks; ++c) {
-    if (c + 1 < chunks) fetch(c + 1);
-    const float* row = &tile[c & 1][lane * AC_STRIDE];
-    const int t_end = min(AC_T, S - c * AC_T);
-    for (int t = 0; t < t_end; ++t) {
-      const float xf = row[t];
-      const double ax = (double)fabsf(xf);
-      p = fma(g, p, h * ax);
-      q = fma(g, q, h * p);
-      if constexpr (MODE == AC_LADDER) {
-        e = fma(ax, ax, e);
-        pk = fmaxf(pk, fabsf(xf));
-        const int ts = c * AC_T + t;
-        const int L = ts < Sk ? ladder_level(q) : 0;  // the zeros behind a partial slot are not samples
-#pragma unroll
-        for (int j = 0; j < AC_J; ++j) {
-          const bool at = j < L;
-          first[j] = (at && first[j] < 0) ? ts : first[j];
-          last[j] = at ? ts : last[j];
-        }
-      }
-      if constexpr (MODE == AC_FINAL) {
-        const int ts = c * AC_T + t;
-        const bool at = ts < Sk && q >= cstar;
-        first_c = (at && first_c < 0) ? ts : first_c;
-        last_c = at ? ts : last_c;
+      for (int j = 0; j < AC_J; ++j) {
+        const bool at = j < L;
+        first[j] = (at && first[j] < 0) ? ts : first[j];
+        last[j] = at ? ts : last[j];
       }
     }
-    if (c + 1 < chunks) park(c + 1);  // the other buffer: its last readers passed the barrier of the previous round
-    __syncthreads();
-  }
+    if constexpr (MODE == AC_FINAL) {
+      const bool at = ts < Sk && q >= cstar;
+      first_c = (at && first_c < 0) ? ts : first_c;
+      last_c = at ? ts : last_c;
+    }
+  });
   if constexpr (MODE == AC_ZERO) {
     if (k < n_full) {
       state[slot * 2 + 0] = p;
@@ -169,44 +120,6 @@ __global__ __launch_bounds__(AC_SEGS) void envelope_kernel(const float* __restri
   }
 }
 
-// Pass 2, one wavefront per utterance: state[u][k] holds end_k and gets s_k, the state at the start of slot k (a trailing partial
-// slot included: it is run from its true state too).  64 slots at a time: every lane loads its segment's end state, then all
-// lanes walk the same chain in order, lane j keeping the s it sees at step j.
-__global__ __launch_bounds__(64) void envelope_carry_kernel(int64_t n_samples, const int64_t* __restrict__ spans, int S,
-                                                            const double* __restrict__ table, int64_t max_segments, double* __restrict__ state) {
-  const int u = blockIdx.x, lane = threadIdx.x;
-  const ActSpan sp = act_span(spans, u, n_samples);
-  const int64_t n_full = sp.count / S;
-  const int64_t n_slots = (sp.count + S - 1) / S;
-  const double T00 = table[2], T01 = table[3], T10 = table[4], T11 = table[5];
-  double sp_ = 0.0, sq_ = 0.0;
-  double* rows = state + (int64_t)u * max_segments * 2;
-  for (int64_t k0 = 0; k0 < n_slots; k0 += 64) {
-    const int64_t k = k0 + lane;
-    double end_p = 0.0, end_q = 0.0, mine_p = 0.0, mine_q = 0.0;
-    if (k < n_full) {
-      end_p = rows[k * 2 + 0];
-      end_q = rows[k * 2 + 1];
-    }
-    const int steps = (int)min((int64_t)64, n_slots - k0);
-    for (int j = 0; j < steps; ++j) {
-      const double ep = __shfl(end_p, j, 64), eq = __shfl(end_q, j, 64);
-      if (lane == j) {
-        mine_p = sp_;
-        mine_q = sq_;
-      }
-      const double np_ = fma(T01, sq_, fma(T00, sp_, ep));
-      const double nq_ = fma(T11, sq_, fma(T10, sp_, eq));
-      sp_ = np_;
-      sq_ = nq_;
-    }
-    if (k < n_slots) {
-      rows[k * 2 + 0] = mine_p;
-      rows[k * 2 + 1] = mine_q;
-    }
-  }
-}
-
 // Pass 4, one wavefront per utterance.  Lane j < 15 walks the slots in order with the hangover left at threshold j; then the sum
 // of squares in slot order (64 slots loaded by the lanes, added in order by all), the peak, and the levels, the same in every lane.
 __global__ __launch_bounds__(64) void level_kernel(const double* __restrict__ sq, const float* __restrict__ peak, const int32_t* __restrict__ pos,
@@ -215,7 +128,7 @@ __global__ __launch_bounds__(64) void level_kernel(const double* __restrict__ sq
                                                    double* __restrict__ sums, double* __restrict__ stats) {
   __shared__ long long a_lds[16];
   const int u = blockIdx.x, lane = threadIdx.x;
-  const ActSpan sp = act_span(spans, u, n_samples);
+  const WaveSpan sp = load_span(spans, u, n_samples);
   const int64_t n_slots = (sp.count + S - 1) / S;
   const int64_t I = 2 * (int64_t)S;
   const int64_t row0 = (int64_t)u * max_segments;
@@ -285,17 +198,7 @@ __global__ __launch_bounds__(64) void level_kernel(const double* __restrict__ sq
     activity = pow(10.0, (longterm - active) / 10.0);
   }
   float gf = 1.0f;
-  if (!measure_only && has_level && pk > 0.0f) {
-    double gn = pow(10.0, (target - active) / 20.0);
-    const double lim = ceil_lin / (double)pk;
-    const bool limited = lim < gn;
-    if (limited) gn = lim;
-    gf = (float)fmin(gn, 3.4028234663852886e38);
-    if (limited) {
-      // rounding to nearest may have stepped over the ceiling: back off until the fp32 product of the peak sample is under it
-      while ((double)gf * (double)pk > ceil_lin || (double)__fmul_rn(pk, gf) > ceil_lin) gf = nextafterf(gf, 0.0f);
-    }
-  }
+  if (!measure_only && has_level && pk > 0.0f) gf = ceiling_gain(pow(10.0, (target - active) / 20.0), pk, ceil_lin);
   if (lane < AC_J) counts[(int64_t)u * TTS_ACTIVITY_COUNTS + lane] = a;
   if (lane == 0) {
     sums[2 * u + 0] = total;
@@ -318,7 +221,7 @@ __global__ __launch_bounds__(64) void runs_kernel(const int32_t* __restrict__ po
                                                   int64_t max_segments, int max_runs, int64_t* __restrict__ runs, int64_t* __restrict__ counts,
                                                   double* __restrict__ stats) {
   const int u = blockIdx.x, lane = threadIdx.x;
-  const ActSpan sp = act_span(spans, u, n_samples);
+  const WaveSpan sp = load_span(spans, u, n_samples);
   const int64_t n_slots = (sp.count + S - 1) / S;
   const int64_t I = 2 * (int64_t)S;
   const int32_t* pp = pos + (int64_t)u * max_segments * AC_POS + 2 * AC_J;
@@ -361,52 +264,17 @@ __global__ __launch_bounds__(64) void runs_kernel(const int32_t* __restrict__ po
   }
 }
 
-// the host rows: inside the wave, count >= 0; *most = the most slots of an utterance
-static int activity_spans(const char* what, const int64_t* spans_host, int batch, int64_t n_samples, int S, int64_t* most) {
-  TTS_CHECK_ARG(batch >= 0 && batch <= 65535, "%s: batch %d is outside 0 .. 65535", what, batch);
-  TTS_CHECK_ARG(n_samples >= 0, "%s: n_samples is negative", what);
-  TTS_CHECK_ARG(batch == 0 || spans_host, "%s: the host copy of the spans is missing", what);
-  *most = 0;
-  for (int u = 0; u < batch; ++u) {
-    const int64_t b = spans_host[2 * u], c = spans_host[2 * u + 1];
-    TTS_CHECK_ARG(c >= 0, "%s: utterance %d has the negative sample count %lld", what, u, (long long)c);
-    TTS_CHECK_ARG(b >= 0 && b <= n_samples && c <= n_samples - b, "%s: utterance %d (samples %lld .. %lld) does not lie inside the wave of %lld samples",
-                  what, u, (long long)b, (long long)(b + c), (long long)n_samples);
-    const int64_t v = (c + S - 1) / S;
-    if (v > *most) *most = v;
-  }
-  return TTS_OK;
-}
-
-static int activity_rate(const char* what, int S) {
-  TTS_CHECK_ARG(S >= TTS_ACTIVITY_MIN_RATE / 10 && S <= TTS_ACTIVITY_MAX_RATE / 10,
-                "%s: seg_samples %d is outside %d .. %d (a tenth of a sample rate of %d .. %d Hz)", what, S, TTS_ACTIVITY_MIN_RATE / 10,
-                TTS_ACTIVITY_MAX_RATE / 10, TTS_ACTIVITY_MIN_RATE, TTS_ACTIVITY_MAX_RATE);
-  return TTS_OK;
-}
-
-// the checks the two calls that read the wave share -> *groups workgroups per utterance (0: nothing to launch)
-static int activity_grid(const char* what, const int64_t* spans_host, int batch, int64_t n_samples, int S, int64_t max_segments, int64_t* groups) {
-  if (int rc = activity_rate(what, S)) return rc;
-  int64_t most = 0;
-  if (int rc = activity_spans(what, spans_host, batch, n_samples, S, &most)) return rc;
-  TTS_CHECK_ARG(max_segments >= 1 && max_segments >= most, "%s: max_segments %lld is below the %lld segments of the longest utterance", what,
-                (long long)max_segments, (long long)most);
-  *groups = (most + AC_SEGS - 1) / AC_SEGS;
-  TTS_CHECK_ARG(*groups <= 0x7fffffff, "%s: more than 2^31 - 1 workgroups per utterance", what);
-  return TTS_OK;
-}
-
 int activity_envelope(const float* x, int64_t n_samples, const int64_t* spans, const int64_t* spans_host, int batch, int S, const double* table,
                       int64_t max_segments, double* state, double* sq, float* peak, int32_t* pos, hipStream_t st) {
+  if (int rc = check_rate("activity_envelope", S, TTS_ACTIVITY_MIN_RATE, TTS_ACTIVITY_MAX_RATE)) return rc;
   int64_t groups = 0;
-  if (int rc = activity_grid("activity_envelope", spans_host, batch, n_samples, S, max_segments, &groups)) return rc;
+  if (int rc = segment_grid("activity_envelope", spans_host, batch, n_samples, S, max_segments, &groups)) return rc;
   if (batch == 0 || groups == 0) return TTS_OK;
   TTS_CHECK_ARG(x && spans && table && state && sq && peak && pos, "activity_envelope: null pointer");
-  const dim3 grid((unsigned)groups, (unsigned)batch), block(AC_SEGS);
+  const dim3 grid((unsigned)groups, (unsigned)batch), block(SEG_LANES);
   hipLaunchKernelGGL((envelope_kernel<AC_ZERO>), grid, block, 0, st, x, n_samples, spans, S, table, max_segments, state, sq, peak, pos,
                      (const double*)nullptr);
-  hipLaunchKernelGGL(envelope_carry_kernel, dim3((unsigned)batch), dim3(64), 0, st, n_samples, spans, S, table, max_segments, state);
+  hipLaunchKernelGGL((segment_carry_kernel<2, true>), dim3((unsigned)batch), dim3(64), 0, st, n_samples, spans, S, table + 2, max_segments, state);
   hipLaunchKernelGGL((envelope_kernel<AC_LADDER>), grid, block, 0, st, x, n_samples, spans, S, table, max_segments, state, sq, peak, pos,
                      (const double*)nullptr);
   return launch_status("activity_envelope");
@@ -414,17 +282,12 @@ int activity_envelope(const float* x, int64_t n_samples, const int64_t* spans, c
 
 int activity_level(const double* sq, const float* peak, const int32_t* pos, int64_t n_samples, const int64_t* spans, int batch, int S,
                    int64_t max_segments, double target, double ceiling, int64_t* counts, double* sums, double* stats, hipStream_t st) {
-  if (int rc = activity_rate("activity_level", S)) return rc;
-  TTS_CHECK_ARG(batch >= 0 && batch <= 65535 && n_samples >= 0 && max_segments >= 1,
-                "activity_level: batch %d is outside 0 .. 65535, n_samples negative or max_segments below 1", batch);
+  if (int rc = check_rate("activity_level", S, TTS_ACTIVITY_MIN_RATE, TTS_ACTIVITY_MAX_RATE)) return rc;
+  double ceil_lin = 1.0;
+  if (int rc = check_target("activity_level", "dB", batch, n_samples, max_segments, target, ceiling, &ceil_lin)) return rc;
   const bool measure_only = target != target;
-  if (!measure_only) {
-    TTS_CHECK_ARG(isfinite(target) && isfinite(ceiling), "activity_level: the target %g dB and the peak ceiling %g dBFS must be finite", target, ceiling);
-    TTS_CHECK_ARG(ceiling <= 0.0, "activity_level: the peak ceiling %g dBFS is above full scale", ceiling);
-  }
   if (batch == 0) return TTS_OK;
   TTS_CHECK_ARG(sq && peak && pos && spans && counts && sums && stats, "activity_level: null pointer");
-  const double ceil_lin = measure_only ? 1.0 : pow(10.0, ceiling / 20.0);
   hipLaunchKernelGGL(level_kernel, dim3((unsigned)batch), dim3(64), 0, st, sq, peak, pos, n_samples, spans, S, max_segments, measure_only ? 1 : 0,
                      measure_only ? 0.0 : target, ceil_lin, counts, sums, stats);
   return launch_status("activity_level");
@@ -433,14 +296,15 @@ int activity_level(const double* sq, const float* peak, const int32_t* pos, int6
 int activity_runs(const float* x, int64_t n_samples, const int64_t* spans, const int64_t* spans_host, int batch, int S, const double* table,
                   int64_t max_segments, const double* state, int32_t* pos, int max_runs, int64_t* runs, int64_t* counts, double* stats,
                   hipStream_t st) {
+  if (int rc = check_rate("activity_runs", S, TTS_ACTIVITY_MIN_RATE, TTS_ACTIVITY_MAX_RATE)) return rc;
   int64_t groups = 0;
-  if (int rc = activity_grid("activity_runs", spans_host, batch, n_samples, S, max_segments, &groups)) return rc;
+  if (int rc = segment_grid("activity_runs", spans_host, batch, n_samples, S, max_segments, &groups)) return rc;
   TTS_CHECK_ARG(max_runs >= 0, "activity_runs: max_runs %d is negative", max_runs);
   if (batch == 0) return TTS_OK;
   TTS_CHECK_ARG(spans && counts && stats && (max_runs == 0 || runs), "activity_runs: null pointer");
   if (groups > 0) {
     TTS_CHECK_ARG(x && table && state && pos, "activity_runs: null pointer");
-    const dim3 grid((unsigned)groups, (unsigned)batch), block(AC_SEGS);
+    const dim3 grid((unsigned)groups, (unsigned)batch), block(SEG_LANES);
     hipLaunchKernelGGL((envelope_kernel<AC_FINAL>), grid, block, 0, st, x, n_samples, spans, S, table, max_segments, const_cast<double*>(state),
                        (double*)nullptr, (float*)nullptr, pos, (const double*)stats);
   }
@@ -452,7 +316,7 @@ int activity_runs(const float* x, int64_t n_samples, const int64_t* spans, const
 }  // namespace tts
 
 extern "C" {
-int tts_activity_tile_segments(void) { return tts::AC_SEGS; }
+int tts_activity_tile_segments(void) { return tts::SEG_LANES; }
 int tts_activity_envelope(const float* x, int64_t n_samples, const int64_t* spans, const int64_t* spans_host, int32_t batch, int32_t seg_samples,
                           const double* table, int64_t max_segments, double* state, double* sq, float* peak, int32_t* pos, tts_stream_t stream) {
   return tts::activity_envelope(x, n_samples, spans, spans_host, batch, seg_samples, table, max_segments, state, sq, peak, pos,

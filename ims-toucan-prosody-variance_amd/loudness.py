@@ -13,24 +13,13 @@ import math
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, segments
+from .segments import MAX_RATE, MIN_RATE, SegmentMeter, segment_samples  # noqa: F401  (the rates are part of this module's surface)
 
 LOUDNESS_COLUMNS = ("lufs", "peak", "blocks", "blocks_abs", "blocks_both", "momentary_max_lufs", "gain", "lufs_after")
-MIN_RATE, MAX_RATE = capi.LOUDNESS_MIN_RATE, capi.LOUDNESS_MAX_RATE
 
 SHELF_F0, SHELF_GAIN_DB, SHELF_Q, SHELF_VB_EXPONENT = 1681.974450955533, 3.999843853973347, 0.7071752369554196, 0.4996667741545416
 HIGHPASS_F0, HIGHPASS_Q = 38.13547087602444, 0.5003270373238773
-
-
-def segment_samples(sr):
-    """Samples of one 100 ms segment.  ValueError for a rate that is no multiple of 10 in 8 000 .. 192 000."""
-    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) and not (isinstance(sr, float) and sr.is_integer()):
-        raise ValueError(f"the loudness meter takes a sample rate that is a multiple of 10 in {MIN_RATE} .. {MAX_RATE} Hz, not {sr!r}")
-    sr = int(sr)
-    if sr % 10 or not MIN_RATE <= sr <= MAX_RATE:
-        raise ValueError(f"the loudness meter takes a sample rate that is a multiple of 10 in {MIN_RATE} .. {MAX_RATE} Hz "
-                         f"(100 ms segments of a whole number of samples), not {sr}")
-    return sr // 10
 
 
 def k_weighting(sr):
@@ -68,38 +57,16 @@ def kernel_table(sr):
 
 
 def check_target(target_lufs, peak_ceiling_dbfs):
-    for name, v in (("target", target_lufs), ("peak ceiling", peak_ceiling_dbfs)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-            raise ValueError(f"the loudness {name} must be a finite number, not {v!r}")
-    if peak_ceiling_dbfs > 0:
-        raise ValueError(f"the peak ceiling {peak_ceiling_dbfs!r} dBFS is above full scale (0 dBFS)")
+    segments.check_target("loudness", target_lufs, peak_ceiling_dbfs)
 
 
-class LoudnessMeter:
+class LoudnessMeter(SegmentMeter):
     """``measure(packed_wave, spans, sr)`` and ``normalize(packed_wave, spans, sr, target_lufs, peak_ceiling_dbfs)`` for a ragged
     batch on the device.  The tables (coefficients and M) are uploaded once per rate and kept.  ``last_segments``: (e_k float64,
     max |x| float32), each [B, most segments of an utterance] on the device, of the last call."""
 
     def __init__(self, device):
-        self.lib = capi.lib()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise capi.ToucanHipError(f"device {str(self.device)!r}: the loudness meter runs on the GPU only")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.tile_segments = int(self.lib.tts_loudness_tile_segments())
-        self._tables = {}
-
-    def table(self, sr):
-        if int(sr) not in self._tables:
-            self._tables[int(sr)] = torch.from_numpy(kernel_table(sr)).to(self.device)
-        return self._tables[int(sr)]
-
-    def _rows(self, wave, spans):
-        assert wave.dtype == torch.float32 and wave.dim() == 1 and wave.device == self.device and wave.is_contiguous()
-        rows = np.ascontiguousarray(np.asarray([(int(b), int(n)) for b, n in spans], dtype=np.int64).reshape(-1, 2))
-        # from pinned memory, so that the copy queues behind the work already on the stream instead of waiting for it
-        return rows, torch.from_numpy(rows).pin_memory().to(self.device, non_blocking=True)
+        super().__init__(device, "loudness meter", kernel_table, "tts_loudness_tile_segments")
 
     def _measure(self, wave, rows, rows_d, sr, target, ceiling):
         """kweight + gate on the current stream -> stats [B, 8] float64 on the device."""
@@ -107,7 +74,7 @@ class LoudnessMeter:
         stats = torch.empty((B, len(LOUDNESS_COLUMNS)), dtype=torch.float64, device=self.device)
         if B == 0:
             return stats
-        max_segments = max(1, int(-(-rows[:, 1].max() // S)))
+        max_segments = self._max_segments(rows, S)
         state = torch.empty((B, max_segments, 4), dtype=torch.float64, device=self.device)
         energy = torch.empty((B, max_segments), dtype=torch.float64, device=self.device)
         peak = torch.empty((B, max_segments), dtype=torch.float32, device=self.device)
@@ -138,13 +105,4 @@ class LoudnessMeter:
         check_target(target_lufs, peak_ceiling_dbfs)
         rows, rows_d = self._rows(packed_wave, spans)
         stats = self._measure(packed_wave, rows, rows_d, sr, target_lufs, peak_ceiling_dbfs)
-        if out is None:
-            tiled = len(rows) > 0 and int(rows[0, 0]) == 0 and int(rows[-1].sum()) == packed_wave.numel() and \
-                bool((rows[1:, 0] == rows[:-1].sum(axis=1)).all())
-            out = torch.empty_like(packed_wave) if tiled else packed_wave.clone()
-        assert out.dtype == torch.float32 and out.shape == packed_wave.shape and out.device == self.device and out.is_contiguous()
-        if len(rows):
-            capi.check(self.lib.tts_apply_gain(packed_wave.data_ptr(), packed_wave.numel(), rows_d.data_ptr(), rows.ctypes.data, len(rows),
-                                               int(rows[:, 1].max()), stats.data_ptr(), out.data_ptr(),
-                                               torch.cuda.current_stream(self.device).cuda_stream), "tts_apply_gain")
-        return out, stats
+        return self._apply_gain(packed_wave, rows, rows_d, stats, out), stats
