@@ -97,8 +97,11 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
 __device__ __forceinline__ float bf16_to_f32(unsigned short u) { return __builtin_bit_cast(float, (unsigned int)u << 16); }
 
 // 16-bit element formats of the MFMA paths: bf16 (compute 1) or IEEE fp16 (compute 2, v_mfma_f32_32x32x16_f16).  Both convert
-// round-to-nearest-even, two values per instruction (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).  fp16 does not saturate: the
-// callers keep everything that can leave its range (flow state, norm statistics, accumulators) in fp32.
+// round-to-nearest-even, two values per instruction (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).  fp16 does not saturate: above 65504
+// the conversion gives inf, below 2^-14 it rounds into subnormals (kept by the conversion, the LDS reads and the MFMAs: measured
+// down to inputs of 2^-22, tests/test_gpu_dynamic_range.py).  The callers keep what leaves that window in a trained model (flow
+// state, norm statistics, accumulators) in fp32; an fp16 operand or 16-bit HBM tensor is finite for inputs up to 2^13 times unit
+// scale and spends the format's own budget down to 2^-14 ("The 16-bit kernels over the dynamic range").
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

@@ -10,9 +10,11 @@
 
 namespace tts {
 
-// The sine is one hardware v_sin_f32 (argument in revolutions, reduced by v_fract_f32): absolute error ~1e-6 for phases up to
-// a few hundred radians (tests/test_gpu_kernels.py::test_snake_aa checks it against the fp64 emulator), versus ~1e-7 for
-// ocml's sinf at 5x the cost and 3x the registers.
+// The sine is one hardware v_sin_f32 (argument in revolutions, reduced by v_fract_f32): absolute error ~1e-6, versus ~1e-7 for
+// ocml's sinf at 5x the cost and 3x the registers.  The phase itself is an fp32 product: it is off by 2 |phase| 2^-24 and by
+// e^alpha times the fp32 error of u, which at 500 radians (log alpha raised by 4) is 3e-4 in y.  Checked against float64 up to
+// there, inside a bound made of those terms and a sine good to 2e-6 (tests/test_gpu_dynamic_range.py: 0.13 of the bound at most;
+// tests/test_gpu_kernels.py::test_snake_aa at phases of ten radians).
 
 // out[i] = snake_aa(x)[t0 + i] for i < ROWS; t0 is the local frame index inside an utterance of T frames; load(q) returns
 // frame q of the utterance (0 <= q < T, already clamped).  t0 may be negative / rows may lie beyond T: those outputs are

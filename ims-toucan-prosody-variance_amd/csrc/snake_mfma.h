@@ -16,8 +16,12 @@
 // Per 16 frames x 16 channels: 2 + 2 MFMAs (64 matrix-pipe cycles) and ~55 VALU instructions, against ~420 VALU instructions of
 // the register-streamed form (snake_stream in snake.h), and the matrix pipe runs beside the VALU.
 //
-// Both filters run in fp16 whatever the conv precision: bf16 activations are exact in fp16 (8-bit mantissa into 11; the vocoder's
-// activations are O(1), far inside fp16's range), the taps carry up to 2^-12 relative error and s is rounded to 11 bits.  For
+// Both filters run in fp16 whatever the conv precision: bf16 activations are exact in fp16 (8-bit mantissa into 11) between 2^-14
+// and 65504 in magnitude, and the vocoder's activations are O(1).  Outside that window the bf16 residual step at C <= 128 has
+// fp16's range, not bf16's: the image overflows for inputs of 2^14 times unit scale (the C = 256 form, fp32 filters, does not), and
+// below 2^-14 it rounds into fp16 subnormals - at 2^-18 the step's error is 6e-3 of the output's rms instead of bf16's 2.8e-3, at
+// 2^-22 8.8e-2 (tests/test_gpu_dynamic_range.py; DESIGN.md section 4, "The 16-bit kernels over the dynamic range").  The taps
+// carry up to 2^-12 relative error and s is rounded to 11 bits.  For
 // the bf16 conv operand this feeds, that is below its 8-bit rounding: the residual step's error against float64 is 0.90 - 0.93 of
 // what the model with fp32 filters gives (conv1's output also waits in fp16, not bf16).  For COMPUTE_F16 it is NOT small: the
 // operand has the same 11 bits, and the step's rms error is 1.23 (C = 64, asymmetric test filter) to 1.96 - 2.21 times (C = 32 /
@@ -148,7 +152,9 @@ struct SnakeFir {
     }
     // u + b sin^2(theta) = (u + b/2) - (b/2) cos(2 theta), theta = u e^alpha: the up-sampler's accumulators START from b/2 (a free add),
     // the phase comes out of one fma ((u + b/2) (e^alpha / pi) - (b/2) (e^alpha / pi), in revolutions), and the result out of one
-    // more: four vector operations per sample instead of five - in a kernel whose first limit is vector issue.
+    // more: four vector operations per sample instead of five - in a kernel whose first limit is vector issue.  The price: u is
+    // rounded to fp32 beside b/2, an absolute error of about 2^-25 b, which shows only where s already sits among fp16's subnormals
+    // (inputs below 2^-14: the rounding model's option snake_offset_sum, tests/abi_emulator.py).
     const float hb = 0.5f * inv_b, er2 = 2.0f * er, c0 = -hb * er2;
     const f32x4v z = {hb, hb, hb, hb};
     const f32x4v u0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a0), __builtin_bit_cast(f16x8, x), z, 0, 0, 0);

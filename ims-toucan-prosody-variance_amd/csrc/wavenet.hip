@@ -247,8 +247,10 @@ __global__ __launch_bounds__(256) void wavenet_layer_kernel(const TtsWavenetDesc
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const float av = aa[4 * rq + q] + bav[q] + pa[q], gvv = ag[4 * rq + q] + bgv[q] + pg[q];
-          // hardware exp / reciprocal (a few ulp, far below the 16-bit rounding of acts): with one wavefront per SIMD the
-          // library tanhf / expf / IEEE division of 48 elements per lane were 6 us of a 37 us launch
+          // hardware exp / reciprocal (a few ulp of 1 + e^-2a: tanh carries an ABSOLUTE error of about 2^-24, far below the 16-bit
+          // rounding of acts for |a| above 2^-14 and above it below - the rounding model's option fast_gate, tests/abi_emulator.py;
+          // DESIGN.md section 4, "The 16-bit kernels over the dynamic range"): with one wavefront per SIMD the library tanhf /
+          // expf / IEEE division of 48 elements per lane were 6 us of a 37 us launch
           const float th = 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * av)) - 1.0f;
           v[q] = th * __builtin_amdgcn_rcpf(1.0f + __expf(-gvv));
         }

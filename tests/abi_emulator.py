@@ -119,25 +119,77 @@ def _snake_fir_matrices(T, filt):
     return np.float32(2.0) * U, D
 
 
-def _snake_seq_mfma(X, alpha, beta, filt):
-    """_snake_seq with the rounding points of the matrix-core snake (csrc/snake_mfma.h:19-26, 63-67, 154-163, 209-210): the constants
-    U and D and the 2x-rate samples s are fp16, both products accumulate in fp32 (float64 here).  X [T, c] holds fp16 values."""
+def _snake_seq_mfma(X, alpha, beta, filt, offset_sum=False):
+    """_snake_seq with the rounding points of the matrix-core snake (csrc/snake_mfma.h:19-30, 67-71, 158-170, 216-217): the constants
+    U and D and the 2x-rate samples s are fp16, both products accumulate in fp32 (float64 here).  X [T, c] holds fp16 values.
+    offset_sum: s as csrc/snake_mfma.h:153-169 forms it, (u + b/2) - (b/2) cos(2 u e^alpha) with b = 1 / (e^beta + 1e-9): the
+    up-sampler's fp32 accumulators start from b/2, so u is rounded to fp32 beside b/2 (an absolute 2^-25 b or so, where u itself is
+    small), the phase is one fp32 fma of that sum and s one more."""
     U, D = (_round16(m, True).astype(np.float64) for m in _snake_fir_matrices(X.shape[0], filt))
-    ea = np.exp(alpha.astype(np.float64))
-    ib = 1.0 / (np.exp(beta.astype(np.float64)) + 1e-9)
     u = U @ X
-    s = _round16((u + ib * np.sin(u * ea) ** 2).astype(np.float32), True).astype(np.float64)
-    return D @ s
+    if offset_sum:
+        f32 = np.float32
+        hb = f32(0.5) * (f32(1.0) / (np.exp(beta.astype(f32)) + f32(1e-9)))
+        er2 = f32(2.0) * (np.exp(alpha.astype(f32)) * f32(0.15915494309189535))  # revolutions of 2 theta per unit of u
+        c0 = -hb * er2
+        up = (u + hb.astype(np.float64)).astype(f32)
+        rev = (up.astype(np.float64) * er2.astype(np.float64) + c0.astype(np.float64)).astype(f32)  # (one fma)
+        cs = np.cos(2.0 * np.pi * (rev - np.floor(rev)).astype(np.float64)).astype(f32)
+        s = (up.astype(np.float64) - hb.astype(np.float64) * cs.astype(np.float64)).astype(f32)      # (one fma)
+    else:
+        ea = np.exp(alpha.astype(np.float64))
+        ib = 1.0 / (np.exp(beta.astype(np.float64)) + 1e-9)
+        s = (u + ib * np.sin(u * ea) ** 2).astype(np.float32)
+    return D @ _round16(s, True).astype(np.float64)
+
+
+def _layernorm_f32(v, g, b, eps, lane_order=False):
+    """LayerNorm over the last axis with every step rounded to fp32 as csrc/ffn.hip:79-102, 200-226 compute it: mean, the squared
+    deviations from it summed by fma, 1 / sqrt, (v - mean) rstd g + b (the last product and sum one fma).
+    lane_order (192 channels): the sums in the order of the kernel's second LayerNorm - a lane holds channels 32 j + 8 rq + 4 lk + i of
+    its frame for one lk, adds (c0 + c1) + (c2 + c3) of every (j, rq) to a running sum, its squares one by one, and the two
+    halves of a frame meet in one addition.  Otherwise numpy's pairwise sums (the first LayerNorm feeds a 16-bit rounding)."""
+    f32, f64 = np.float32, np.float64
+    v = np.asarray(v, dtype=f32)
+    rows, c = v.shape
+    n = f32(1.0 / c)
+    if lane_order:
+        assert c == 192
+        h = v.reshape(rows, 6, 4, 2, 4).transpose(0, 3, 1, 2, 4).reshape(rows, 2, 24, 4)  # [row, lk, (j, rq), i]
+        s = np.zeros((rows, 2), f32)
+        for m in range(24):
+            s = s + ((h[:, :, m, 0] + h[:, :, m, 1]) + (h[:, :, m, 2] + h[:, :, m, 3]))
+        mean = ((s[:, 0] + s[:, 1]) * n)[:, None]
+        e = v - mean
+        eh = e.reshape(rows, 6, 4, 2, 4).transpose(0, 3, 1, 2, 4).reshape(rows, 2, 96)
+        q = np.zeros((rows, 2), f32)
+        for m in range(96):
+            q = (eh[:, :, m].astype(f64) ** 2 + q.astype(f64)).astype(f32)
+        q = (q[:, 0] + q[:, 1])[:, None]
+    else:
+        mean = v.sum(1, keepdims=True, dtype=f32) * n
+        e = v - mean
+        q = (e * e).sum(1, keepdims=True, dtype=f32)
+    assert mean.dtype == f32 and e.dtype == f32 and q.dtype == f32
+    rstd = f32(1.0) / np.sqrt((q.astype(f64) * f64(n) + f64(f32(eps))).astype(f32))
+    return ((e * rstd).astype(f64) * g.astype(f64) + b.astype(f64)).astype(f32)
 
 
 class Emulator:
-    def __init__(self, mfma_snake=False):
-        """mfma_snake: model the rounding points that tts_resblock_step's matrix-core snake (C <= 128) adds to the ones in
+    def __init__(self, mfma_snake=False, snake_offset_sum=False, fast_gate=False, f32_norms=False):
+        """Options name what a kernel form does beyond the rounding points in its entry's docstring; all off by default.
+        snake_offset_sum (with mfma_snake): the matrix-core snake's s as the kernel forms it, see _snake_seq_mfma.
+        fast_gate: tts_wavenet_layer's gate as csrc/wavenet.hip:250-255 computes it, tanh(a) = 2 / (1 + e^(-2a)) - 1 and the sigmoid
+        with every step rounded to fp32 - an absolute error of 2^-24 or so on tanh, where the float64 gate's is relative.
+        f32_norms: tts_ffn_fused's two LayerNorms in fp32 (_layernorm_f32) as the kernel computes them; float64 otherwise.
+        mfma_snake: model the rounding points that tts_resblock_step's matrix-core snake (C <= 128) adds to the ones in
         tts_resblock_step's docstring.  csrc/resblock.hip:403-415 stores the raw x of act1 as an fp16 LDS image (`pack16<true>`, exact
-        for 16-bit x) and :677-690 rounds conv1's output to fp16 in both formats (`as_f16`); csrc/snake_mfma.h:19-26 keeps the filter
+        for fp16 x, and for bf16 x between 2^-14 and 65504 in magnitude: below it rounds into fp16 subnormals, above it is inf)
+        and :677-690 rounds conv1's output to fp16 in both formats (`as_f16`); csrc/snake_mfma.h:19-30 keeps the filter
         constants and the 2x-rate samples s in fp16 (see _snake_seq_mfma).  Off (the default), the model is the one the VALU snake
         follows: fp32 x, fp32 taps, fp32 s, conv1's output in the compute format."""
         self.mfma_snake = bool(mfma_snake)
+        self.snake_offset_sum, self.fast_gate, self.f32_norms = bool(snake_offset_sum), bool(fast_gate), bool(f32_norms)
         self._real = None
         self._err = b""
         self.calls = {}
@@ -264,7 +316,14 @@ class Emulator:
             cond = _mat(d.cond, se, 384, d.ld_cond)[sb:se]
             a = (acc[:, :H] + b1[:H]) + cond[:, :H]
             g = (acc[:, H:] + b1[H:]) + cond[:, H:]
-            acts = _round16((np.tanh(a.astype(np.float64)) / (1.0 + np.exp(-g.astype(np.float64)))).astype(np.float32), f16).astype(np.float64)
+            if self.fast_gate:
+                one, f32 = np.float32(1.0), np.float32
+                th = np.float32(2.0) * (one / (one + np.exp(-2.0 * a.astype(np.float64)).astype(f32))) - one
+                gate = th * (one / (one + np.exp(-g.astype(np.float64)).astype(f32)))
+                assert gate.dtype == f32
+            else:
+                gate = (np.tanh(a.astype(np.float64)) / (1.0 + np.exp(-g.astype(np.float64)))).astype(np.float32)
+            acts = _round16(gate, f16).astype(np.float64)
             out = ((acts @ w2).astype(np.float32) + b2) + hs[:, col0:col0 + n2]
             _mat(d.hs_out, se, 384, d.ld_out)[sb:se, col0:col0 + n2] = out
         return 0
@@ -300,6 +359,8 @@ class Emulator:
         x = _mat(d.x, d.rows, Cc, d.ldx)[:d.rows].astype(np.float32)
         ln = lambda v, g, b: (((v - v.mean(1, keepdims=True, dtype=np.float64)) / np.sqrt(v.astype(np.float64).var(1, keepdims=True) + d.eps))
                               * _arr(g, Cc).astype(np.float64) + _arr(b, Cc).astype(np.float64)).astype(np.float32)
+        if self.f32_norms:
+            ln = lambda v, g, b: _layernorm_f32(v, _arr(g, Cc), _arr(b, Cc), d.eps, lane_order=g == d.post_g)
         xn = _round16(ln(x, d.ln_g, d.ln_b), f16).astype(np.float64)
         h = _round16(np.maximum((xn @ w1.T).astype(np.float32) + b1, 0.0), f16).astype(np.float64)
         out = x + np.float32(d.alpha) * ((h @ w2.T).astype(np.float32) + _arr(d.b2, Cc).astype(np.float32))
@@ -340,7 +401,7 @@ class Emulator:
 
         def act(v, al, be):
             if mfma:
-                return _snake_seq_mfma(v, _arr(al, C_), _arr(be, C_), filt)
+                return _snake_seq_mfma(v, _arr(al, C_), _arr(be, C_), filt, self.snake_offset_sum)
             if snake:
                 return _snake_seq(v, _arr(al, C_), _arr(be, C_), filt)
             return np.where(v > 0, v, v * np.float64(np.float32(d.slope)))

@@ -123,8 +123,9 @@ class Report:
         return "\n".join([self.line()] + [f"  ({c}) {m}" for c in sorted(self.failed) for m in self.failed[c]])
 
 
-def evaluate(name, fmt, g, e, r, row_class, m, classes=(EDGE, SEAM, INTERIOR)):
-    """Checks (a) to (c) on one case; g, e, r: [live rows, channels].  Never raises for a failed check: see `check`."""
+def evaluate(name, fmt, g, e, r, row_class, m, classes=(EDGE, SEAM, INTERIOR), unit=None):
+    """Checks (a) to (c) on one case; g, e, r: [live rows, channels].  Never raises for a failed check: see `check`.
+    unit: the u of check (c) where it is not the format's own (tests/dynamic_range.py: never below it)."""
     g, e, r = (np.asarray(a, dtype=np.float64) for a in (g, e, r))
     assert g.shape == e.shape == r.shape and g.ndim == 2 and g.shape[0] == len(row_class)
     assert np.isfinite(g).all() and np.isfinite(e).all() and np.isfinite(r).all(), f"{name}: non-finite values"
@@ -147,7 +148,8 @@ def evaluate(name, fmt, g, e, r, row_class, m, classes=(EDGE, SEAM, INTERIOR)):
             rep.fail("b", f"stratum '{sname}' ({n} elements): E_g {sg:.4e} > (1 + {m:.2f}) x E_e {se:.4e} (ratio {sg / se:.4f})")
     rep.worst = worst
     rep.gain_g, rep.gain_e = gain(g, r), gain(e, r)
-    u = UNIT[fmt]
+    u = UNIT[fmt] if unit is None else unit
+    assert u >= UNIT[fmt]
     if abs(rep.gain_g - rep.gain_e) > 0.1 * u:
         rep.fail("c", f"gain(g) {rep.gain_g:+.4e} - gain(e) {rep.gain_e:+.4e} = {rep.gain_g - rep.gain_e:+.3e}, beyond 0.1 u = {0.1 * u:.3e}")
     return rep

@@ -1,10 +1,13 @@
 """A stand-in kernel for the test of the error-budget test (tests/test_error_budget_cpu.py): the rounding model of
 tests/abi_emulator.py with the arithmetic the kernels' comments describe - fp32 accumulation in 16-channel k-steps, tap-major - for
-tts_conv1d, tts_wavenet_layer and tts_resblock_step, and six ways of being subtly wrong (`MUTANTS`).  Host memory only.
+tts_conv1d, tts_wavenet_layer and tts_resblock_step, and ways of being subtly wrong (`MUTANTS`: six that show at unit scale, and
+`RANGE_MUTANTS`: two that show only away from it, tests/test_dynamic_range_cpu.py).  Host memory only.
 
 Only what the error-budget cases use is restated: the 16-bit products, LINEAR / GLU / GATED, the three prologues, bias, pre-add,
 residual, 16-bit tensors.  Anything else is an assertion error.
 """
+import contextlib
+
 import numpy as np
 
 from ims_toucan_prosody_variance_amd import capi
@@ -18,6 +21,30 @@ MUTANTS = {
     "halo_neighbour": "v: the two halo rows (one where the halo is one row) in front of an utterance's first tile taken from the rows in front of it in the packed layout",
     "gate_twice": "vi: the gate rounded to 16 bits twice: sigmoid -> 16 bits, then tanh x sigmoid -> 16 bits",
 }
+# Wrong only away from unit scale: the levels of tests/dynamic_range.py are there to see them.
+RANGE_MUTANTS = {
+    "flush_subnormals": "vii: every conversion to fp16 flushes what lies below fp16's smallest normal number (2^-14) to zero - the fp16 formats, and the "
+                        "fp16 images of the matrix-core snake's model in either format",
+    "phase_from_16bit": "viii: the snake's phase sin(u e^alpha) taken from u rounded to 16 bits; the model takes the fp32 u",
+}
+F16_MIN_NORMAL = np.float32(2.0 ** -14)
+
+
+def _flush16(a):
+    """round-to-nearest-even to fp16 with subnormal results flushed to zero, as float32."""
+    h = np.ascontiguousarray(a, dtype=np.float32).astype(np.float16).astype(np.float32)
+    return np.where(np.abs(h) < F16_MIN_NORMAL, np.float32(0.0) * h, h)
+
+
+@contextlib.contextmanager
+def _model_flushes_fp16():
+    """The rounding model's own conversions to fp16 flush, for as long as the block lasts."""
+    orig = ae._round16
+    ae._round16 = lambda a, f16: _flush16(a) if f16 else orig(a, f16)
+    try:
+        yield
+    finally:
+        ae._round16 = orig
 
 
 def _truncate16(a, f16):
@@ -32,12 +59,14 @@ def _truncate16(a, f16):
 class StandIn(ae.Emulator):
     def __init__(self, mutant=None, **kw):
         super().__init__(**kw)
-        assert mutant is None or mutant in MUTANTS
+        assert mutant is None or mutant in MUTANTS or mutant in RANGE_MUTANTS
         self.mutant = mutant
 
     # ---- shared pieces ---------------------------------------------------------------------------------------------------------
     def r16(self, a, f16):
         a = np.asarray(a, dtype=np.float32)
+        if self.mutant == "flush_subnormals" and f16:
+            return _flush16(a)
         return _truncate16(a, f16) if self.mutant == "truncate" else ae._round16(a, f16)
 
     def bias(self, ptr, n):
@@ -67,7 +96,7 @@ class StandIn(ae.Emulator):
                 acc += (rows[:, k0:k0 + 16] @ w[j, k0:k0 + 16].astype(np.float64)).astype(np.float32)
         return acc
 
-    def snake(self, X, alpha, beta, filt):
+    def snake(self, X, alpha, beta, filt, f16):
         """abi_emulator._snake_seq through the folded filter matrices (fp32 taps, float64 sums)."""
         T = X.shape[0]
         U, D = (m.astype(np.float64) for m in ae._snake_fir_matrices(T, filt))
@@ -77,7 +106,8 @@ class StandIn(ae.Emulator):
         ea = np.exp(alpha.astype(np.float64))
         ib = 1.0 / (np.exp(beta.astype(np.float64)) + 1e-9)
         u = U @ X.astype(np.float64)
-        return D @ (u + ib * np.sin(u * ea) ** 2)
+        phase_u = self.r16(u, f16).astype(np.float64) if self.mutant == "phase_from_16bit" else u
+        return D @ (u + ib * np.sin(phase_u * ea) ** 2)
 
     @staticmethod
     def weights(ptr, taps, cin_pad, wn, f16):
@@ -99,7 +129,7 @@ class StandIn(ae.Emulator):
             if d.pre_act == capi.PRE_LRELU:
                 x = np.where(x > 0, x, x * np.float32(d.pre_slope))
             elif d.pre_act == capi.PRE_SNAKE:
-                x = self.snake(x, ae._arr(d.snake_alpha, d.cin), ae._arr(d.snake_beta, d.cin), ae._arr(d.snake_filt, 12)).astype(np.float32)
+                x = self.snake(x, ae._arr(d.snake_alpha, d.cin), ae._arr(d.snake_beta, d.cin), ae._arr(d.snake_filt, 12), f16).astype(np.float32)
             return self.r16(x, f16)
 
         for sb, se, sid in ae._seqs_from_tiles(ae._tiles(d.tiles, d.n_tiles)):
@@ -152,7 +182,11 @@ class StandIn(ae.Emulator):
     # ---- tts_resblock_step -----------------------------------------------------------------------------------------------------
     def tts_resblock_step(self, dref, stream):
         d = dref._obj
-        assert not self.mfma_snake and not d.accumulate
+        if self.mfma_snake:  # the matrix-core snake's model as it stands (float64 sums), its fp16 conversions flushing for mutant vii
+            assert self.mutant in (None, "flush_subnormals")
+            with _model_flushes_fp16() if self.mutant else contextlib.nullcontext():
+                return super().tts_resblock_step(dref, stream)
+        assert not d.accumulate
         C_, k = d.c, d.taps
         f16 = d.compute == capi.COMPUTE_F16
         io = ae._fmt(d.io_bf16, f16)
@@ -164,7 +198,7 @@ class StandIn(ae.Emulator):
 
         def act(v, al, be):
             if snake:
-                return self.snake(v, ae._arr(al, C_), ae._arr(be, C_), filt).astype(np.float32)
+                return self.snake(v, ae._arr(al, C_), ae._arr(be, C_), filt, f16).astype(np.float32)
             return np.where(v > 0, v, v * np.float32(d.slope))
 
         for sb, se, sid in ae._seqs_from_tiles(ae._tiles(d.tiles, d.n_tiles)):
