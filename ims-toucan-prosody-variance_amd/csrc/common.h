@@ -86,6 +86,36 @@ struct WavenetBlock {
 int wavenet_block(const WavenetBlock& d, hipStream_t st);
 int wavenet_block_tile_rows();
 
+// The Conformer convolution module in one launch (conformer_conv.hip): y = x + pw2(swish(dwconv_bn(glu(pw1(LN(x)))))), width 192,
+// depthwise kernel 31 (the decoder's), bit-identical to tts_layernorm + tts_conv1d (GLU) + tts_dwconv_swish + tts_conv1d (residual) on the
+// 16-bit path.  y is a different buffer than x: a workgroup reads the halo rows that its neighbours own.  pw1 / pw2 as packed for
+// tts_conv1d's 16-bit path ([1][24][w_n][8]; pw1's gate half starts at column w1_half, its bias is [value 192 | gate 192]).
+// The tile table has conformer_conv_tile_rows(kernel) rows per tile.
+struct ConformerConv {
+  const float* x; int ld_x;
+  float* y; int ld_y;
+  const float *ln_g, *ln_b; float eps;
+  const void* w1; int w1_n; int w1_half; const float* b1;
+  const float *dw_w, *dw_b; int kernel;  // [kernel][192] (BatchNorm folded), [192]
+  const void* w2; int w2_n; const float* b2;
+  const TtsTile* tiles; int n_tiles; int tile_rows;
+  int compute;
+};
+int conformer_conv(const ConformerConv& d, hipStream_t st);
+int conformer_conv_tile_rows(int kernel);
+
+// LayerNorm and a 1-tap 192 -> cout conv (cout a multiple of 96) in one launch (conformer_conv.hip): y = W LN(x) + bias, fp32 out,
+// bit-identical to tts_layernorm + tts_conv1d on the 16-bit path.  w as packed for tts_conv1d ([1][24][w_n][8]); 128-row tile table.
+struct LnLinear {
+  const float* x; int ld_x;
+  float* y; int ld_y;
+  const float *ln_g, *ln_b; float eps;
+  const void* w; int w_n; const float* bias; int cout;
+  const TtsTile* tiles; int n_tiles; int tile_rows;
+  int compute;
+};
+int ln_linear(const LnLinear& d, hipStream_t st);
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));

@@ -729,6 +729,45 @@ int ffn_fused(Handle* h, const Dev* fused, const ConvW& w1, const ConvW& w2, con
                      (double)R * ATT * 8 + (double)fused->bytes, (double)R * ATT, st, [&] { return tts_ffn_fused(&d, st); });
 }
 
+// norm_mha + the q | k | v projection in one launch (ln_linear, conformer_conv.hip): the bits of tts_layernorm + tts_conv1d
+int ln_qkv(Handle* h, const Block& b, const float* x, float* qkv, const Layout& l, const TileTab& t128, hipStream_t st) {
+  LnLinear d;
+  memset(&d, 0, sizeof(d));
+  d.x = x; d.ld_x = ATT; d.y = qkv; d.ld_y = 3 * ATT;
+  d.ln_g = b.ln_g[1]; d.ln_b = b.ln_b[1]; d.eps = 1e-12f;
+  d.w = b.qkv.w16; d.w_n = b.qkv.wn; d.bias = b.qkv.bias; d.cout = b.qkv.cout;
+  d.tiles = t128.dev; d.n_tiles = t128.n; d.tile_rows = 128;
+  d.compute = b.qkv.compute16;
+  double rows = 0;
+  for (int n : l.lengths) rows += n;
+  return prof_launch(h, d.compute == TTS_COMPUTE_F16 ? "ln_qkv_f16" : "ln_qkv_bf16", 2.0 * rows * ATT * d.cout,
+                     rows * (ATT + d.cout) * 4 + 2.0 * ATT * d.cout, rows * d.cout, st, [&] { return ln_linear(d, st); });
+}
+
+// The convolution module in one launch (conformer_conv.hip): x <- x2 + pw2(swish(dwconv_bn(glu(pw1(LN(x2))))))
+int conv_module(Handle* h, const Block& b, int kernel, const float* x2, float* x, const Layout& l, const TileTab& tcc, hipStream_t st) {
+  ConformerConv d;
+  memset(&d, 0, sizeof(d));
+  d.x = x2; d.ld_x = ATT; d.y = x; d.ld_y = ATT;
+  d.ln_g = b.ln_g[2]; d.ln_b = b.ln_b[2]; d.eps = 1e-12f;
+  d.w1 = b.pw1.w16; d.w1_n = b.pw1.wn; d.w1_half = b.pw1.half_pad; d.b1 = b.pw1.bias;
+  d.dw_w = b.dw_w; d.dw_b = b.dw_b; d.kernel = kernel;
+  d.w2 = b.pw2.w16; d.w2_n = b.pw2.wn; d.b2 = b.pw2.bias;
+  d.tiles = tcc.dev; d.n_tiles = tcc.n; d.tile_rows = conformer_conv_tile_rows(kernel);
+  d.compute = b.pw1.compute16;
+  double rows = 0;
+  for (int n : l.lengths) rows += n;
+  return prof_launch(h, d.compute == TTS_COMPUTE_F16 ? "conformer_conv_f16" : "conformer_conv_bf16", 2.0 * rows * ATT * (3 * ATT + kernel),
+                     rows * ATT * 8 + 2.0 * 3 * ATT * ATT, rows * ATT, st, [&] { return conformer_conv(d, st); });
+}
+
+// Which stacks run the fused launches (16-bit configurations; [0] encoder, [1] decoder).  The bits are the same either way: a speed
+// choice per stack, never per batch or row count.  The decoder (31 taps, 640-frame utterances: seven 98-row tiles each) gains from
+// both; the encoder (128-phoneme utterances: 2 x 32 workgroups on 256 CUs, each one a 128-row chain) measured SLOWER fused -
+// + 0.08 ms per pass for either part - so it keeps the stand-alone launches.
+constexpr bool FUSE_LN_QKV[2] = {false, true};
+constexpr bool FUSE_CONV_MODULE[2] = {false, true};
+
 // Layers/EncoderLayer.py:62-144 x 6 on the residual stream x [rows, 192] (already scaled by sqrt(192))
 int conformer(Handle* h, int stack, float* x, const Layout& l, Arena& a, hipStream_t st) {
   const int R = l.total, kernel = stack ? 31 : 7;
@@ -743,9 +782,15 @@ int conformer(Handle* h, int stack, float* x, const Layout& l, Arena& a, hipStre
   TTS_ALLOC(ctx, a, float, (size_t)R * ATT);
   TTS_ALLOC(glu, a, float, (size_t)R * ATT);
   TTS_ALLOC(dwo, a, float, (size_t)R * ATT);
-  TileTab t128, t64;
+  TileTab t128, t64, tcc;
   TTS_TRY(tiles_of(h, l, 128, st, &t128));
   TTS_TRY(tiles_of(h, l, 64, st, &t64));
+  const int fuse_mask = (FUSE_LN_QKV[stack] ? 1 : 0) | (FUSE_CONV_MODULE[stack] ? 2 : 0);
+  if (b16 == 16 && (fuse_mask & 2)) TTS_TRY(tiles_of(h, l, conformer_conv_tile_rows(kernel), st, &tcc));  // (98 rows at 31 taps)
+  // a packed 1-tap 192 -> n conv the fused kernels can read: the handle's 16-bit format, with a bias
+  auto fusable = [&](const ConvW& c, int mode, int cout) {
+    return c.w16 && c.bias && c.compute16 == h->cfg.precision && c.mode == mode && c.taps == 1 && c.cin == ATT && c.cin_pad == ATT && c.cout == cout;
+  };
   const size_t prow = (size_t)(2 * h->pmax - 1) * ATT;
   for (int bi = 0; bi < 6; ++bi) {
     const Block& b = (stack ? h->acoustic.dec : h->acoustic.enc)[bi];
@@ -765,19 +810,34 @@ int conformer(Handle* h, int stack, float* x, const Layout& l, Arena& a, hipStre
       TTS_TRY(conv(h, b.ffm2, T2(hid, 1536, b16), T2(x, ATT), l, st, half));
     }
     // relative-position self-attention (:93-116)
-    TTS_TRY(tts_layernorm(x, ATT, ln, ATT, b.ln_g[1], b.ln_b[1], R, ATT, 1e-12f, st));
-    TTS_TRY(conv(h, b.qkv, T2(ln, ATT), T2(qkv, 3 * ATT), l, st));
+    // (16-bit configurations: norm_mha inside the projection, and the convolution module as one launch - native only, same bits)
+    const bool fuse_qkv = b16 == 16 && (fuse_mask & 1) && fusable(b.qkv, TTS_MODE_LINEAR, 3 * ATT);
+    const bool fuse_conv = b16 == 16 && (fuse_mask & 2) && fusable(b.pw1, TTS_MODE_GLU, ATT) && fusable(b.pw2, TTS_MODE_LINEAR, ATT);
+    if (fuse_qkv) {
+      TTS_TRY(ln_qkv(h, b, x, qkv, l, t128, st));
+    } else {
+      TTS_TRY(tts_layernorm(x, ATT, ln, ATT, b.ln_g[1], b.ln_b[1], R, ATT, 1e-12f, st));
+      TTS_TRY(conv(h, b.qkv, T2(ln, ATT), T2(qkv, 3 * ATT), l, st));
+    }
     if (b16 == 16)  // (16-bit configurations: the contractions on the fp16 matrix cores)
       TTS_TRY(tts_relpos_attention_f16(qkv, 3 * ATT, h->ptab[stack] + bi * prow, h->pmax, b.u, b.v, ctx, ATT, HEADS, DK, t128.dev, t128.n, 128, st));
     else
       TTS_TRY(tts_relpos_attention(qkv, 3 * ATT, h->ptab[stack] + bi * prow, h->pmax, b.u, b.v, ctx, ATT, HEADS, DK, t128.dev, t128.n, 128,
                                    h->split_mode == 2 ? TTS_ATT_KEY_SPLIT_ALWAYS : (h->split_mode == 1 ? TTS_ATT_KEY_SPLIT : 0), st));
-    TTS_TRY(conv(h, b.out, T2(ctx, ATT), T2(x, ATT), l, st, res1));
     // convolution module (:119-125, Convolution.py:31-55)
-    TTS_TRY(tts_layernorm(x, ATT, ln, ATT, b.ln_g[2], b.ln_b[2], R, ATT, 1e-12f, st));
-    TTS_TRY(conv(h, b.pw1, T2(ln, ATT), T2(glu, ATT), l, st));
-    TTS_TRY(tts_dwconv_swish(glu, ATT, dwo, ATT, b.dw_w, b.dw_b, ATT, kernel, t64.dev, t64.n, 64, st));
-    TTS_TRY(conv(h, b.pw2, T2(dwo, ATT), T2(x, ATT), l, st, res1));
+    if (fuse_conv) {
+      // The fused module cannot update x in place (a workgroup reads its neighbours' rows as halo), so the out projection leaves
+      // x + out(ctx) in the (otherwise unused) glu buffer and the module writes x: x keeps the bits it has today in every row,
+      // the gap rows between utterances included; the buffer's gap rows are never read (halos are clamped to the utterance).
+      TTS_TRY(conv(h, b.out, T2(ctx, ATT), T2(glu, ATT), l, st, res1));
+      TTS_TRY(conv_module(h, b, kernel, glu, x, l, tcc, st));
+    } else {
+      TTS_TRY(conv(h, b.out, T2(ctx, ATT), T2(x, ATT), l, st, res1));
+      TTS_TRY(tts_layernorm(x, ATT, ln, ATT, b.ln_g[2], b.ln_b[2], R, ATT, 1e-12f, st));
+      TTS_TRY(conv(h, b.pw1, T2(ln, ATT), T2(glu, ATT), l, st));
+      TTS_TRY(tts_dwconv_swish(glu, ATT, dwo, ATT, b.dw_w, b.dw_b, ATT, kernel, t64.dev, t64.n, 64, st));
+      TTS_TRY(conv(h, b.pw2, T2(dwo, ATT), T2(x, ATT), l, st, res1));
+    }
     // feed-forward (:128-133) and the block's final norm (:135-136)
     if (fuse_ffn && b.ff_fused) {  // (with the block's final norm in its epilogue)
       TTS_TRY(ffn_fused(h, b.ff_fused, b.ff1, b.ff2, b.ln_g[3], b.ln_b[3], b.ln_g[4], b.ln_b[4], x, R, st));

@@ -2,10 +2,11 @@
 // strided over the lanes so every global access is a contiguous 256-B segment; reductions are wave
 // shuffles (no LDS).  All statistics in fp32, two-pass (mean, then centred second moment) like ATen.
 #include "common.h"
+#include "conformer_ops.h"
 
 namespace tts {
 
-constexpr int MAX_PER_LANE = 8;  // channels <= 512
+constexpr int MAX_PER_LANE = LN_MAX_PER_LANE;  // channels <= 512
 
 // Layers/LayerNorm.py:24-36 (eps 1e-12, LayerNorm.py:17)
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,
@@ -15,29 +16,20 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float* xr = x + (size_t)row * ldx;
-  float v[MAX_PER_LANE];
-  float s = 0.f;
+  float v[1][LN_MAX_PER_LANE], g[LN_MAX_PER_LANE], b[LN_MAX_PER_LANE], o[1][LN_MAX_PER_LANE];
 #pragma unroll
-  for (int i = 0; i < MAX_PER_LANE; ++i) {
+  for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
     const int ch = lane + 64 * i;
-    v[i] = ch < c ? xr[ch] : 0.f;
-    s += v[i];
+    v[0][i] = ch < c ? xr[ch] : 0.f;
+    g[i] = ch < c ? gamma[ch] : 0.f;
+    b[i] = ch < c ? beta[ch] : 0.f;
   }
-  const float mean = wave_sum(s) / (float)c;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < MAX_PER_LANE; ++i) {
-    const int ch = lane + 64 * i;
-    const float dlt = ch < c ? v[i] - mean : 0.f;
-    q += dlt * dlt;
-  }
-  const float var = wave_sum(q) / (float)c;
-  const float rstd = 1.0f / sqrtf(var + eps);
+  layernorm_rows<1>(v, lane, c, eps, g, b, o);
   float* yr = y + (size_t)row * ldy;
 #pragma unroll
-  for (int i = 0; i < MAX_PER_LANE; ++i) {
+  for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
     const int ch = lane + 64 * i;
-    if (ch < c) yr[ch] = (v[i] - mean) * rstd * gamma[ch] + beta[ch];
+    if (ch < c) yr[ch] = o[0][i];
   }
 }
 

@@ -3,6 +3,7 @@
 // contiguous in memory, so a wavefront touches whole 256-B segments), sliding windows live in registers
 // (static unrolling), halos are resolved per utterance through the tile table.
 #include "common.h"
+#include "conformer_ops.h"
 #include "snake.h"
 
 namespace tts {
@@ -36,10 +37,7 @@ __global__ __launch_bounds__(256) void dwconv_swish_kernel(const float* __restri
 #pragma unroll
     for (int i = 0; i < ROWS; ++i) {
       if (r0 + i >= t.seq_end) break;
-      float a = bias;
-#pragma unroll
-      for (int j = 0; j < K; ++j) a = fmaf(wk[j], win[i + j], a);
-      y[(size_t)(r0 + i) * ldy + ch] = a * (1.0f / (1.0f + expf(-a)));
+      y[(size_t)(r0 + i) * ldy + ch] = dwconv_swish_value(wk, win, i, bias);
     }
   }
 }
