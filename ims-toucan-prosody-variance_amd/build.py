@@ -6,7 +6,7 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libtoucan_hip.so")
-SOURCES = ["conv1d.hip", "conv1d_wide.hip", "resblock.hip", "rowops.hip", "attention_mfma.hip", "sequence_ops.hip", "capi.hip", "pipeline.hip", "style.hip", "wavenet.hip", "ffn.hip", "conformer_conv.hip", "align.hip", "score.hip", "gan.hip", "pitch.hip", "train.hip", "resample.hip", "glow_forward.hip", "prosody.hip", "prosody_curves.hip", "compare.hip", "loudness.hip", "activity.hip"]
+SOURCES = ["conv1d.hip", "conv1d_wide.hip", "resblock.hip", "rowops.hip", "attention_mfma.hip", "sequence_ops.hip", "capi.hip", "pipeline.hip", "style.hip", "wavenet.hip", "ffn.hip", "conformer_conv.hip", "align.hip", "score.hip", "gan.hip", "pitch.hip", "train.hip", "resample.hip", "glow_forward.hip", "prosody.hip","compare.hip", "loudness.hip", "activity.hip"]
 
 
 def _hipcc():

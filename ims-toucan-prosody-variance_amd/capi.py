@@ -249,7 +249,7 @@ PROSODY_PROTOTYPES = {
 }
 PROSODY_SCALES, PROSODY_STATS = 4, 8  # include/toucan_prosody.h TTS_PROSODY_SCALES, TTS_PROSODY_STATS
 
-# symbol -> (restype, argtypes); mirrors include/toucan_prosody_curves.h (per-phoneme prosody curves: csrc/prosody_curves.hip, stage entries in csrc/pipeline.hip)
+# symbol -> (restype, argtypes); mirrors include/toucan_prosody_curves.h (per-phoneme prosody curves: csrc/prosody.hip, stage entries in csrc/pipeline.hip)
 CURVE_PROTOTYPES = {
     "tts_prosody_control_c": (C.c_int, [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "tts_control_and_regulate_c": (C.c_int, [_p, _p, _p, _p, _i, _p, _p]),

@@ -37,7 +37,6 @@ int relpos_attention_f16(const float*, int, const float*, int, const float*, con
                           int, hipStream_t);
 int dwconv_swish(const float*, int, float*, int, const float*, const float*, int, int, const TtsTile*, int, int, hipStream_t);
 int duration_from_log(const float*, int*, int, hipStream_t);
-int prosody_control(const float*, int, float*, float*, int*, const int*, const int*, int, float, float, float, float, hipStream_t);
 int length_regulate(const float*, int, const float*, const float*, const float*, const float*, const float*, const float*,
                     const int*, const int*, const int*, const int*, int, int, int, int, float*, int, float*, int, float, hipStream_t);
 int glow_invconv_actnorm(float*, int, int, int, const float*, const float*, const float*, hipStream_t);
@@ -129,13 +128,6 @@ int tts_dwconv_swish(const float* x, int32_t ldx, float* y, int32_t ldy, const f
 
 int tts_duration_from_log(const float* logd, int32_t* dur, int32_t n, tts_stream_t stream) {
   return tts::duration_from_log(logd, dur, n, ST(stream));
-}
-
-int tts_prosody_control(const float* text, int32_t ld_text, float* pitch, float* energy, int32_t* dur, const int32_t* seq_begin,
-                        const int32_t* seq_end, int32_t n_seq, float duration_scale, float pitch_scale, float energy_scale,
-                        float pause_scale, tts_stream_t stream) {
-  return tts::prosody_control(text, ld_text, pitch, energy, dur, seq_begin, seq_end, n_seq, duration_scale, pitch_scale, energy_scale,
-                              pause_scale, ST(stream));
 }
 
 int tts_length_regulate(const float* enc, int32_t ld_enc, const float* pitch, const float* energy, const float* wp, const float* bp,

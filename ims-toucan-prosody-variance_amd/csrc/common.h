@@ -201,6 +201,16 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// Sum over a workgroup of 256: the butterfly within each wavefront, then the four wavefronts added 0 + 1 + 2 + 3.  red: 4 floats of
+// LDS.  Every thread of the workgroup must call it (two barriers), and all get the same sum.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -204,9 +204,9 @@ struct Handle {
   int* dur = nullptr;
   float *cat = nullptr, *dec = nullptr, *mel0 = nullptr, *mel = nullptr;
   std::vector<int> frames;  // per utterance, after the control step
-  float* pstats = nullptr;           // [2][B][TTS_PROSODY_STATS] in the phoneme arena: before | after the scales (tts_control_and_regulate_v)
-  std::vector<float> pstats_host;    // the same, read back with the durations; empty if the batch went through the scalar entry
-  float* cstats = nullptr;           // [before | after][B][8], then [before | after][n_spans][8], room for B + R rows twice (tts_control_and_regulate_c)
+  float* pstats = nullptr;           // in the phoneme arena, room for B + R rows twice: [before | after][B][TTS_PROSODY_STATS], then
+                                     // [before | after][n_spans][TTS_PROSODY_STATS] (tts_control_and_regulate_v and _c)
+  std::vector<float> pstats_host;    // the utterance blocks, read back with the durations; empty if the batch went through the scalar entry
   int n_spans = -1;                  // spans of the last tts_control_and_regulate_c of the batch in flight; -1: it did not run
   std::vector<float> sstats_host;    // [2][n_spans][TTS_PROSODY_STATS], read back with the durations
   bool have_flow = false;
@@ -228,7 +228,7 @@ namespace {
 bool is16(const Handle* h);
 
 // the stages after tts_encoder read the model it resolved: a tts_load_weights call since then (it may have freed a tensor) ends the pass
-#define TTS_CHECK_RESOLVED(h, entry) TTS_CHECK_ARG((h)->acoustic.resolved, entry ": weights were loaded since tts_encoder: run it again")
+#define TTS_CHECK_RESOLVED(h, entry) TTS_CHECK_ARG((h)->acoustic.resolved, "%s: weights were loaded since tts_encoder: run it again", entry)
 
 int hip_ok(hipError_t e, const char* what) {
   if (e == hipSuccess) return TTS_OK;
@@ -856,8 +856,8 @@ size_t conformer_bytes(size_t R) { return R * (ATT * 4 * 4 + 1536 * 4 + 3 * ATT 
 // Arena sizes: ONE set of expressions for the stage entries (what they reserve) and for tts_workspace_bytes (what it promises).
 size_t phone_arena_bytes(size_t R, size_t B) {
   return conformer_bytes(R) + R * (100 + 3 * ATT + 6 * 256 + 16) * 4 + B * (64 + 2 * ATT + 24 * 256 + 8) * 4 + (1 << 16) +
-         2 * B * TTS_PROSODY_STATS * 4 + 256 +  // (the two statistics blocks of tts_control_and_regulate_v)
-         2 * (B + R) * TTS_PROSODY_STATS * 4 + 256;  // (those of tts_control_and_regulate_c: utterances and at most R spans)
+         2 * (B + R) * TTS_PROSODY_STATS * 4 + 256 +  // (the statistics blocks of tts_control_and_regulate_v and _c: utterances, at most R spans)
+         2 * B * TTS_PROSODY_STATS * 4 + 256;  // (once a second statistics buffer; kept, so that tts_workspace_bytes answers as it did)
 }
 // cond_buffer: the PostFlow keeps the coupling blocks' conditioning [RS, 1536] in memory (every configuration but the 16-bit ones
 // with the fused WaveNet layer, which computes it inside the layer).  Those configurations run a coupling block as one launch: the
@@ -1015,7 +1015,6 @@ int pipeline_encoder(Handle* h, const float* text, const float* utt_emb, const i
   h->have_flow = false;
   h->pstats = nullptr;
   h->pstats_host.clear();
-  h->cstats = nullptr;
   h->n_spans = -1;
   h->sstats_host.clear();
   const int R = h->lp.total;
@@ -1146,141 +1145,105 @@ int regulate(Handle* h, const int* dur_dev, bool gold, int* frames_out, hipStrea
 }
 
 // ---- stage A.3 / B.0: control, the one host round trip, length regulator -----------------------------------------------
-int pipeline_control_regulate(Handle* h, float duration_scale, float pitch_scale, float energy_scale, float pause_scale,
-                              int* frames_out, hipStream_t st) {
-  TTS_CHECK_ARG(h && h->enc && h->dur, "tts_control_and_regulate: run tts_encoder and tts_variance_predictors first");
-  TTS_CHECK_ARG(duration_scale > 0.f, "tts_control_and_regulate: duration_scaling_factor must be positive");
-  TTS_CHECK_RESOLVED(h, "tts_control_and_regulate");
-  h->tab_which = 0;
-  const int *pb, *pe;
-  TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
-  TTS_TRY(tts_prosody_control(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, h->B, duration_scale, pitch_scale, energy_scale, pause_scale, st));
-  return regulate(h, h->dur, false, frames_out, st);
+// What one of the three entries asks for (include/toucan_tts.h, toucan_prosody.h, toucan_prosody_curves.h).
+struct ControlRequest {
+  const char* entry;                      // its name, for messages
+  enum { BATCH, UTTERANCE, PHONEME } kind;  // the scalar, the _v, the _c entry; the last two take the statistics
+  float batch[4] = {1.f, 1.f, 1.f, 1.f};  // the scalar entry's scales: duration, pitch variance, energy variance, pause
+  const float* scales = nullptr;          // host [B][4]: UTTERANCE, and optional with PHONEME
+  const float* curves = nullptr;          // host [R][5]: PHONEME only
+  const int* spans = nullptr;             // host [n_spans][2] packed row ranges, with curves only
+  int n_spans = 0;
+};
+
+// A host array goes up through the table store of the acoustic stages under the key name + bytes (pinned staging, one asynchronous
+// copy on st).  The store already orders the reuse of its staging behind the last use of a generation, and a table that repeats -
+// an emphasis sweep run twice, a server's handful of presets - is found there, not uploaded; one that never repeats costs its bytes
+// once in the store and once in the key until the generation passes TABLE_BUDGET and is rewound.  (A layout key is 4 (2 n + 1)
+// bytes of begins and lengths, these start with a name: the two kinds never collide.)
+template <class T>
+int table_named(Handle* h, const char* name, const T* host, size_t n, hipStream_t st, const T** dev) {
+  std::string key(name);
+  key.append(reinterpret_cast<const char*>(host), n * sizeof(T));
+  void* d;
+  TTS_TRY(table_of(h, key, st, [&] { return std::vector<T>(host, host + n); }, &d, nullptr));
+  *dev = static_cast<const T*>(d);
+  return TTS_OK;
 }
 
-// ---- stage A.3 / B.0 with per-utterance scales (include/toucan_prosody.h) ------------------------------------------------------
-// overrides -> statistics -> scales -> statistics, then regulate(): its duration read-back is the one host round trip, and the
-// statistics ride on it (their copy is enqueued in front of it).  scales: host [B][4]; they go up through the table store of the
-// acoustic stages (pinned staging, one asynchronous copy on st; a batch that repeats a table of scales finds it there).
-int pipeline_control_regulate_v(Handle* h, const float* scales, int* frames_out, hipStream_t st) {
-  TTS_CHECK_ARG(h && h->enc && h->dur, "tts_control_and_regulate_v: run tts_encoder and tts_variance_predictors first");
-  TTS_CHECK_ARG(scales, "tts_control_and_regulate_v: null scales");
-  const int B = h->B;
-  for (int u = 0; u < B; ++u) {
-    const float ds = scales[(size_t)u * TTS_PROSODY_SCALES];
-    TTS_CHECK_ARG(std::isfinite(ds) && ds > 0.f, "tts_control_and_regulate_v: utterance %d: duration_scaling_factor %g must be positive and finite",
-                  u, (double)ds);
+// Scalar entry: one control launch, then regulate().  Per-utterance entries: overrides -> statistics (utterances, spans) -> scales
+// and curves -> statistics (utterances, spans), then regulate(): its duration read-back is the one host round trip, and the
+// statistics ride on it (their copies are enqueued in front of it).  Nothing is enqueued before every value has been checked.
+int control_regulate(Handle* h, const ControlRequest& q, int* frames_out, hipStream_t st) {
+  TTS_CHECK_ARG(h && h->enc && h->dur, "%s: run tts_encoder and tts_variance_predictors first", q.entry);
+  const int B = h->B, R = h->lp.total, n_spans = q.n_spans;
+  if (q.kind == ControlRequest::BATCH) TTS_CHECK_ARG(q.batch[0] > 0.f, "%s: duration_scaling_factor must be positive", q.entry);
+  if (q.kind == ControlRequest::UTTERANCE) TTS_CHECK_ARG(q.scales, "%s: null scales", q.entry);
+  if (q.kind == ControlRequest::PHONEME) {
+    TTS_CHECK_ARG(q.curves, "%s: null curves", q.entry);
+    TTS_CHECK_ARG(n_spans >= 0 && (q.spans || n_spans == 0), "%s: %d spans and %s span table", q.entry, n_spans, q.spans ? "a" : "no");
+    TTS_CHECK_ARG(n_spans <= R, "%s: %d spans, the entry takes at most one per phoneme row (%d)", q.entry, n_spans, R);
   }
-  TTS_CHECK_RESOLVED(h, "tts_control_and_regulate_v");
-  h->tab_which = 0;
-  const int *pb, *pe;
-  TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
-  // (a layout key is 4 (2 n + 1) bytes long, this one 14 + 16 B: the two kinds never collide)
-  std::string key("prosody_scales");
-  key.append(reinterpret_cast<const char*>(scales), (size_t)B * TTS_PROSODY_SCALES * sizeof(float));
-  void* sdev;
-  TTS_TRY(table_of(h, key, st, [&] { return std::vector<float>(scales, scales + (size_t)B * TTS_PROSODY_SCALES); }, &sdev, nullptr));
-  const size_t NS = (size_t)B * TTS_PROSODY_STATS;
-  if (!h->pstats) {
-    TTS_ALLOC(ps, h->phone, float, 2 * NS);
-    h->pstats = ps;
-  }
-  float *before = h->pstats, *after = h->pstats + NS;
-  TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, nullptr, st));
-  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, before, st));
-  TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, static_cast<const float*>(sdev), st));
-  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, after, st));
-  h->pstats_host.assign(2 * NS, 0.f);
-  TTS_TRY(hip_ok(hipMemcpyAsync(h->pstats_host.data(), h->pstats, 2 * NS * sizeof(float), hipMemcpyDeviceToHost, st), "prosody statistics to host"));
-  const int rc = regulate(h, h->dur, false, frames_out, st);  // (synchronises st once: the durations and the statistics are on the host)
-  if (rc != TTS_OK) h->pstats_host.clear();
-  return rc;
-}
-
-// ---- stage A.3 / B.0 with a per-phoneme curve table (include/toucan_prosody_curves.h) -------------------------------------------
-// overrides -> statistics (utterances, spans) -> scales and curves -> statistics (utterances, spans), then regulate().  curves: host
-// [R][5], spans: host [n_spans][2] packed row ranges.  Both go up through the table store of the acoustic stages like the scales of
-// the _v entry (pinned staging, one asynchronous copy each on st): the store already orders the reuse of its staging behind the last
-// use of a generation, which a staging buffer beside the phoneme arena would have to do again, and a table that repeats - an emphasis
-// sweep run twice, a server's handful of presets - is found there, not uploaded.  A table that never repeats costs its 20 B per
-// phoneme once in the store and once in the key until the generation passes TABLE_BUDGET and is rewound.
-int pipeline_control_regulate_c(Handle* h, const float* scales, const float* curves, const int* spans, int n_spans, int* frames_out,
-                                hipStream_t st) {
-  TTS_CHECK_ARG(h && h->enc && h->dur, "tts_control_and_regulate_c: run tts_encoder and tts_variance_predictors first");
-  TTS_CHECK_ARG(curves, "tts_control_and_regulate_c: null curves");
-  TTS_CHECK_ARG(n_spans >= 0 && (spans || n_spans == 0), "tts_control_and_regulate_c: %d spans and %s span table", n_spans, spans ? "a" : "no");
-  const int B = h->B, R = h->lp.total;
-  TTS_CHECK_ARG(n_spans <= R, "tts_control_and_regulate_c: %d spans, the entry takes at most one per phoneme row (%d)", n_spans, R);
   for (int u = 0; u < B; ++u) {
-    if (scales) {
-      const float ds = scales[(size_t)u * TTS_PROSODY_SCALES];
-      TTS_CHECK_ARG(std::isfinite(ds) && ds > 0.f, "tts_control_and_regulate_c: utterance %d: duration_scaling_factor %g must be positive and finite",
-                    u, (double)ds);
+    if (q.scales) {
+      const float ds = q.scales[(size_t)u * TTS_PROSODY_SCALES];
+      TTS_CHECK_ARG(std::isfinite(ds) && ds > 0.f, "%s: utterance %d: duration_scaling_factor %g must be positive and finite", q.entry, u, (double)ds);
     }
-    for (int i = 0; i < h->lp.lengths[u]; ++i) {
-      const float* c = curves + (size_t)(h->lp.begins[u] + i) * TTS_PROSODY_CURVE_COLUMNS;
-      TTS_CHECK_ARG(std::isfinite(c[0]) && c[0] > 0.f, "tts_control_and_regulate_c: utterance %d, phoneme %d: duration factor %g must be positive and finite",
-                    u, i, (double)c[0]);
+    for (int i = 0; q.curves && i < h->lp.lengths[u]; ++i) {
+      const float* c = q.curves + (size_t)(h->lp.begins[u] + i) * TTS_PROSODY_CURVE_COLUMNS;
+      TTS_CHECK_ARG(std::isfinite(c[0]) && c[0] > 0.f, "%s: utterance %d, phoneme %d: duration factor %g must be positive and finite", q.entry, u, i,
+                    (double)c[0]);
       for (int k = 1; k < TTS_PROSODY_CURVE_COLUMNS; ++k)
-        TTS_CHECK_ARG(std::isfinite(c[k]), "tts_control_and_regulate_c: utterance %d, phoneme %d: curve column %d is %g, it must be finite", u, i, k,
-                      (double)c[k]);
+        TTS_CHECK_ARG(std::isfinite(c[k]), "%s: utterance %d, phoneme %d: curve column %d is %g, it must be finite", q.entry, u, i, k, (double)c[k]);
     }
   }
   for (int s = 0; s < n_spans; ++s)
-    TTS_CHECK_ARG(0 <= spans[2 * s] && spans[2 * s] <= spans[2 * s + 1] && spans[2 * s + 1] <= R,
-                  "tts_control_and_regulate_c: span %d is rows [%d, %d), the batch has %d", s, spans[2 * s], spans[2 * s + 1], R);
-  TTS_CHECK_RESOLVED(h, "tts_control_and_regulate_c");
+    TTS_CHECK_ARG(0 <= q.spans[2 * s] && q.spans[2 * s] <= q.spans[2 * s + 1] && q.spans[2 * s + 1] <= R, "%s: span %d is rows [%d, %d), the batch has %d",
+                  q.entry, s, q.spans[2 * s], q.spans[2 * s + 1], R);
+  TTS_CHECK_RESOLVED(h, q.entry);
   h->tab_which = 0;
   const int *pb, *pe;
   TTS_TRY(bounds_of(h, h->lp, st, &pb, &pe));
-  // (keys: a layout key is 4 (2 n + 1) bytes of begins and lengths; these start with a name, as the _v entry's does)
-  void *sdev = nullptr, *cdev = nullptr, *bdev = nullptr;
-  if (scales) {
-    std::string key("prosody_scales");
-    key.append(reinterpret_cast<const char*>(scales), (size_t)B * TTS_PROSODY_SCALES * sizeof(float));
-    TTS_TRY(table_of(h, key, st, [&] { return std::vector<float>(scales, scales + (size_t)B * TTS_PROSODY_SCALES); }, &sdev, nullptr));
+  if (q.kind == ControlRequest::BATCH) {
+    TTS_TRY(tts_prosody_control(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, q.batch[0], q.batch[1], q.batch[2], q.batch[3], st));
+    return regulate(h, h->dur, false, frames_out, st);
   }
-  {
-    std::string key("prosody_curves");
-    key.append(reinterpret_cast<const char*>(curves), (size_t)R * TTS_PROSODY_CURVE_COLUMNS * sizeof(float));
-    TTS_TRY(table_of(h, key, st, [&] { return std::vector<float>(curves, curves + (size_t)R * TTS_PROSODY_CURVE_COLUMNS); }, &cdev, nullptr));
-  }
+  const float *sdev = nullptr, *cdev = nullptr;
+  const int *xb = nullptr, *xe = nullptr;
+  if (q.scales) TTS_TRY(table_named(h, "prosody_scales", q.scales, (size_t)B * TTS_PROSODY_SCALES, st, &sdev));
+  if (q.curves) TTS_TRY(table_named(h, "prosody_curves", q.curves, (size_t)R * TTS_PROSODY_CURVE_COLUMNS, st, &cdev));
   if (n_spans > 0) {  // (begin[n_spans] | end[n_spans]), the form tts_prosody_stats takes
-    std::string key("prosody_spans");
-    key.append(reinterpret_cast<const char*>(spans), (size_t)n_spans * 2 * sizeof(int));
-    TTS_TRY(table_of(h, key, st, [&] {
-      std::vector<int> host(2 * (size_t)n_spans);
-      for (int s = 0; s < n_spans; ++s) {
-        host[s] = spans[2 * s];
-        host[n_spans + s] = spans[2 * s + 1];
-      }
-      return host;
-    }, &bdev, nullptr));
+    std::vector<int> bounds(2 * (size_t)n_spans);
+    for (int s = 0; s < n_spans; ++s) {
+      bounds[s] = q.spans[2 * s];
+      bounds[n_spans + s] = q.spans[2 * s + 1];
+    }
+    TTS_TRY(table_named(h, "prosody_spans", bounds.data(), bounds.size(), st, &xb));
+    xe = xb + n_spans;
   }
-  const int *xb = static_cast<const int*>(bdev), *xe = xb ? xb + n_spans : nullptr;
   const size_t NU = (size_t)B * TTS_PROSODY_STATS, NX = (size_t)n_spans * TTS_PROSODY_STATS;
-  if (!h->cstats) {
-    TTS_ALLOC(cs, h->phone, float, 2 * (size_t)(B + R) * TTS_PROSODY_STATS);
-    h->cstats = cs;
+  if (!h->pstats) {
+    TTS_ALLOC(ps, h->phone, float, 2 * (size_t)(B + R) * TTS_PROSODY_STATS);
+    h->pstats = ps;
   }
-  float *ubefore = h->cstats, *uafter = ubefore + NU, *xbefore = uafter + NU, *xafter = xbefore + NX;
+  float *ubefore = h->pstats, *uafter = ubefore + NU, *xbefore = uafter + NU, *xafter = xbefore + NX;
   TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, nullptr, st));
   TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, ubefore, st));
-  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, xb, xe, n_spans, xbefore, st));
-  TTS_TRY(tts_prosody_control_c(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, static_cast<const float*>(sdev),
-                                static_cast<const float*>(cdev), st));
+  TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, xb, xe, n_spans, xbefore, st));  // (no spans: no launch)
+  if (q.curves) TTS_TRY(tts_prosody_control_c(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, sdev, cdev, st));
+  else TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, sdev, st));
   TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, uafter, st));
   TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, xb, xe, n_spans, xafter, st));
   h->pstats_host.assign(2 * NU, 0.f);
-  h->sstats_host.assign(2 * NX, 0.f);
   TTS_TRY(hip_ok(hipMemcpyAsync(h->pstats_host.data(), ubefore, 2 * NU * sizeof(float), hipMemcpyDeviceToHost, st), "prosody statistics to host"));
+  if (q.curves) h->sstats_host.assign(2 * NX, 0.f);
   if (n_spans > 0)
     TTS_TRY(hip_ok(hipMemcpyAsync(h->sstats_host.data(), xbefore, 2 * NX * sizeof(float), hipMemcpyDeviceToHost, st), "span statistics to host"));
   const int rc = regulate(h, h->dur, false, frames_out, st);  // (synchronises st once: durations and statistics are on the host)
-  h->n_spans = rc == TTS_OK ? n_spans : -1;
-  if (rc != TTS_OK) {
-    h->pstats_host.clear();
-    h->sstats_host.clear();
+  if (rc != TTS_OK) h->pstats_host.clear();
+  if (q.curves) {
+    h->n_spans = rc == TTS_OK ? n_spans : -1;
+    if (rc != TTS_OK) h->sstats_host.clear();
   }
   return rc;
 }
@@ -1753,11 +1716,13 @@ int tts_variance_predictors(TtsHandle* h, const float* gold_pitch, const float* 
 }
 int tts_control_and_regulate(TtsHandle* h, float duration_scale, float pitch_scale, float energy_scale, float pause_scale,
                              int32_t* frame_counts, tts_stream_t stream) {
-  return tts::stage_done(H(h), 0, ST(stream),
-                         tts::pipeline_control_regulate(H(h), duration_scale, pitch_scale, energy_scale, pause_scale, frame_counts, ST(stream)));
+  tts::ControlRequest q{"tts_control_and_regulate", tts::ControlRequest::BATCH, {duration_scale, pitch_scale, energy_scale, pause_scale}};
+  return tts::stage_done(H(h), 0, ST(stream), tts::control_regulate(H(h), q, frame_counts, ST(stream)));
 }
 int tts_control_and_regulate_v(TtsHandle* h, const float* scales, int32_t* frame_counts, tts_stream_t stream) {
-  return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_control_regulate_v(H(h), scales, frame_counts, ST(stream)));
+  tts::ControlRequest q{"tts_control_and_regulate_v", tts::ControlRequest::UTTERANCE};
+  q.scales = scales;
+  return tts::stage_done(H(h), 0, ST(stream), tts::control_regulate(H(h), q, frame_counts, ST(stream)));
 }
 int tts_copy_prosody_stats(TtsHandle* h, float* before, float* after, tts_stream_t stream) {
   (void)stream;  // (the blocks came back with the durations: a host copy)
@@ -1773,7 +1738,12 @@ int tts_copy_prosody_stats(TtsHandle* h, float* before, float* after, tts_stream
 }
 int tts_control_and_regulate_c(TtsHandle* h, const float* scales, const float* curves, const int32_t* spans, int32_t n_spans,
                                int32_t* frame_counts, tts_stream_t stream) {
-  return tts::stage_done(H(h), 0, ST(stream), tts::pipeline_control_regulate_c(H(h), scales, curves, spans, n_spans, frame_counts, ST(stream)));
+  tts::ControlRequest q{"tts_control_and_regulate_c", tts::ControlRequest::PHONEME};
+  q.scales = scales;
+  q.curves = curves;
+  q.spans = spans;
+  q.n_spans = n_spans;
+  return tts::stage_done(H(h), 0, ST(stream), tts::control_regulate(H(h), q, frame_counts, ST(stream)));
 }
 int tts_copy_prosody_span_stats(TtsHandle* h, float* before, float* after, tts_stream_t stream) {
   (void)stream;  // (the blocks came back with the durations: a host copy)

@@ -73,64 +73,6 @@ int duration_from_log(const float* logd, int* dur, int n, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// InferenceToucanTTS.py:214-227 + _scale_variance :333-343.  One workgroup per utterance.
-// Feature columns (Preprocessing/articulatory_features.py:817-901): phoneme 15, silence 16, word-boundary 21, voiced 61.
-// ------------------------------------------------------------------------------------------------
-__device__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ void scale_variance(float* seq, int r0, int r1, float scale, float* red) {
-  // mean over the NON-ZERO entries; every entry (zeros included) is shifted, scaled, shifted back; negatives -> 0
-  float s = 0.f, cnt = 0.f;
-  for (int r = r0 + threadIdx.x; r < r1; r += 256) {
-    const float v = seq[r];
-    if (v != 0.0f) { s += v; cnt += 1.f; }
-  }
-  s = block_sum(s, red);
-  cnt = block_sum(cnt, red);
-  const float avg = s / cnt;  // empty selection -> NaN, as torch's mean of an empty tensor
-  for (int r = r0 + threadIdx.x; r < r1; r += 256) {
-    float v = seq[r] - avg;
-    v = v * scale;
-    v = v + avg;
-    seq[r] = v < 0.0f ? 0.0f : v;
-  }
-}
-
-__global__ __launch_bounds__(256) void prosody_control_kernel(const float* __restrict__ text, int ld_text, float* pitch, float* energy,
-                                                              int* dur, const int* __restrict__ seq_begin, const int* __restrict__ seq_end,
-                                                              float duration_scale, float pitch_scale, float energy_scale, float pause_scale) {
-  __shared__ float red[4];
-  const int u = blockIdx.x;
-  const int r0 = seq_begin[u], r1 = seq_end[u];
-  for (int r = r0 + threadIdx.x; r < r1; r += 256) {
-    const float* f = text + (size_t)r * ld_text;
-    if (f[61] == 0.0f) pitch[r] = 0.0f;
-    if (f[15] == 0.0f) energy[r] = 0.0f;
-    int d = dur[r];
-    if (f[21] == 1.0f) d = 0;
-    if (f[16] == 1.0f && pause_scale != 1.0f) d = (int)rintf((float)d * pause_scale);
-    if (duration_scale != 1.0f) d = (int)rintf((float)d * duration_scale);
-    dur[r] = d;
-  }
-  __syncthreads();
-  if (pitch_scale != 1.0f) scale_variance(pitch, r0, r1, pitch_scale, red);
-  if (energy_scale != 1.0f) scale_variance(energy, r0, r1, energy_scale, red);
-}
-
-int prosody_control(const float* text, int ld_text, float* pitch, float* energy, int* dur, const int* sb, const int* se, int n_seq,
-                    float ds, float ps, float es, float pause, hipStream_t st) {
-  if (n_seq == 0) return TTS_OK;
-  hipLaunchKernelGGL(prosody_control_kernel, dim3(n_seq), dim3(256), 0, st, text, ld_text, pitch, energy, dur, sb, se, ds, ps, es, pause);
-  return launch_status("prosody_control");
-}
-
-// ------------------------------------------------------------------------------------------------
 // LengthRegulator (Layers/LengthRegulator.py:37-61) fused with the pitch/energy embedding add
 // (InferenceToucanTTS.py:230-232).  grid = (frame tiles of 64, utterances).  Every workgroup rebuilds the
 // inclusive scan of its utterance's durations in LDS (L is a few hundred at most), finds the source phoneme

@@ -669,27 +669,28 @@ class AcousticEngine:
             d.copy_(gold_d)
         if taps is not None:
             taps.update(enc_out=enc.clone(), pitch_raw=p.clone(), energy_raw=en.clone())
-        if curves is not None:  # per-phoneme curves: overrides -> statistics (utterances, spans) -> scales and curves -> statistics
-            n = 0 if ranges is None else int(ranges.shape[1])
-            stats, span_stats = ops.empty(2, B, capi.PROSODY_STATS), ops.empty(2, max(n, 1), capi.PROSODY_STATS)
-            ops.prosody_control_v(text, p, en, d, rag_p, None)
-            ops.prosody_stats(p, en, d, rag_p, stats[0])
+        if curves is None and not torch.is_tensor(scales):  # one set of scalars for the batch: no statistics
+            ops.prosody_control(text, p, en, d, rag_p, *scales)
+            return enc, p, en, d
+        # per-utterance scales [B, 4] and / or per-phoneme curves: overrides -> statistics (utterances, spans) -> scales and curves ->
+        # statistics, the launches of tts_control_and_regulate_v / _c in their order
+        n = 0 if ranges is None else int(ranges.shape[1])
+        stats = ops.empty(2, B, capi.PROSODY_STATS)
+        span_stats = None if curves is None else ops.empty(2, max(n, 1), capi.PROSODY_STATS)
+
+        def measure(k):
+            ops.prosody_stats(p, en, d, rag_p, stats[k])
             if n:
-                ops.prosody_span_stats(p, en, d, ranges, span_stats[0])
-            ops.prosody_control_c(text, p, en, d, rag_p, scales, curves)
-            ops.prosody_stats(p, en, d, rag_p, stats[1])
-            if n:
-                ops.prosody_span_stats(p, en, d, ranges, span_stats[1])
-            return enc, p, en, d, stats, span_stats[:, :n]
-        if torch.is_tensor(scales):  # per-utterance scales [B, 4]: overrides -> statistics -> scales -> statistics
-            stats = ops.empty(2, B, capi.PROSODY_STATS)
-            ops.prosody_control_v(text, p, en, d, rag_p, None)
-            ops.prosody_stats(p, en, d, rag_p, stats[0])
+                ops.prosody_span_stats(p, en, d, ranges, span_stats[k])
+
+        ops.prosody_control_v(text, p, en, d, rag_p, None)
+        measure(0)
+        if curves is None:
             ops.prosody_control_v(text, p, en, d, rag_p, scales)
-            ops.prosody_stats(p, en, d, rag_p, stats[1])
-            return enc, p, en, d, stats
-        ops.prosody_control(text, p, en, d, rag_p, *scales)
-        return enc, p, en, d
+        else:
+            ops.prosody_control_c(text, p, en, d, rag_p, scales, curves)
+        measure(1)
+        return (enc, p, en, d, stats) if curves is None else (enc, p, en, d, stats, span_stats[:, :n])
 
     # ---- stage B: length regulator -> decoder -> PostNet -> PostFlow (shapes fixed by the durations) ----------
     def _stage_b(self, enc, p, en, d, z_sq, rag_p, rag_f, taps=None):

@@ -298,28 +298,26 @@ class NativePipeline:
         capi.check(lib.tts_variance_predictors(self.h, ptr(packed["gp"]), ptr(packed["ge"]), ptr(packed["gd"]), st), "tts_variance_predictors")
         frames = (C.c_int32 * B)()
         self._prosody_stats = self._prosody_span_stats = None
-        fptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        if curves is not None:  # per-phoneme curves (include/toucan_prosody_curves.h): both kinds of statistics come back with the durations
+        fptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        if curves is not None:  # per-phoneme curves (include/toucan_prosody_curves.h)
             ctab, ranges, counts = curves
             n = int(ranges.shape[0])
-            capi.check(lib.tts_control_and_regulate_c(self.h, None if table is None else fptr(table), fptr(ctab), fptr(ranges) if n else None, n,
-                                                      frames, st), "tts_control_and_regulate_c")
-            before, after = (np.empty((B, capi.PROSODY_STATS), dtype=np.float32) for _ in range(2))
-            capi.check(lib.tts_copy_prosody_stats(self.h, fptr(before), fptr(after), st), "tts_copy_prosody_stats")
-            sb, sa = (np.empty((n, capi.PROSODY_STATS), dtype=np.float32) for _ in range(2))
-            capi.check(lib.tts_copy_prosody_span_stats(self.h, fptr(sb), fptr(sa), st), "tts_copy_prosody_span_stats")
-            self._prosody_stats = (before, after)
-            self._prosody_span_stats = prosody.split_span_stats((sb, sa), counts)
-            return [int(f) for f in frames]
-        if table is None:
+            capi.check(lib.tts_control_and_regulate_c(self.h, fptr(table), fptr(ctab), fptr(ranges) if n else None, n, frames, st),
+                       "tts_control_and_regulate_c")
+        elif table is not None:  # per-utterance scales (include/toucan_prosody.h)
+            capi.check(lib.tts_control_and_regulate_v(self.h, fptr(table), frames, st), "tts_control_and_regulate_v")
+        else:
             capi.check(lib.tts_control_and_regulate(self.h, float(duration_scale), float(pitch_scale), float(energy_scale), float(pause_scale), frames, st),
                        "tts_control_and_regulate")
             return [int(f) for f in frames]
-        # per-utterance scales (include/toucan_prosody.h): the statistics come back with the durations, inside the entry's one round trip
-        capi.check(lib.tts_control_and_regulate_v(self.h, table.ctypes.data_as(C.c_void_p), frames, st), "tts_control_and_regulate_v")
+        # the statistics came back with the durations, inside the entry's one round trip: host copies
         before, after = (np.empty((B, capi.PROSODY_STATS), dtype=np.float32) for _ in range(2))
-        capi.check(lib.tts_copy_prosody_stats(self.h, before.ctypes.data_as(C.c_void_p), after.ctypes.data_as(C.c_void_p), st), "tts_copy_prosody_stats")
+        capi.check(lib.tts_copy_prosody_stats(self.h, fptr(before), fptr(after), st), "tts_copy_prosody_stats")
         self._prosody_stats = (before, after)
+        if curves is not None:
+            sb, sa = (np.empty((n, capi.PROSODY_STATS), dtype=np.float32) for _ in range(2))
+            capi.check(lib.tts_copy_prosody_span_stats(self.h, fptr(sb), fptr(sa), st), "tts_copy_prosody_span_stats")
+            self._prosody_span_stats = prosody.split_span_stats((sb, sa), counts)
         return [int(f) for f in frames]
 
     @torch.inference_mode()

@@ -1,6 +1,6 @@
 /*
- * toucan_prosody_curves.h - C ABI of the per-phoneme prosody curves in libtoucan_hip.so (kernel: csrc/prosody_curves.hip, stage
- * entries: csrc/pipeline.hip).  toucan_prosody.h gives every utterance of a ragged batch its own four scales; here every PHONEME has
+ * toucan_prosody_curves.h - C ABI of the per-phoneme prosody curves in libtoucan_hip.so (kernel: csrc/prosody.hip, the one the
+ * other two control entries launch; stage entries: csrc/pipeline.hip).  toucan_prosody.h gives every utterance of a ragged batch its own four scales; here every PHONEME has
  * its own: a curve table, float32 [rows][5] over the packed phoneme rows, whose columns are
  *
  *     0 duration factor   1 pitch variance scale   2 energy variance scale   (neutral 1)      3 pitch offset   4 energy offset   (neutral 0)

@@ -9,7 +9,7 @@ The code path each test exists to reach (retire the test with the path):
 * test_length_regulator_*            csrc/sequence_ops.hip length_regulate_kernel: the second and later sweeps of the 256-wide
                                      inclusive scan and their running carry (L = 257, 600, 4096 = LR_MAX_PHONES), runs of zero
                                      durations across a sweep edge, the all-zero utterance beside others; the host's limit check.
-* test_prosody_control_*             prosody_control_kernel / scale_variance: the r += 256 stride loops (1000, 257 rows), the NaN
+* test_prosody_control_*             csrc/prosody.hip prosody_control_kernel / scale_variance: the r += 256 stride loops (1000, 257 rows), the NaN
                                      mean of an all-unvoiced pitch row, scale 0 and scale 1.
 * test_duration_head_*               duration_kernel: both clamps (0 and 1e6), expf next to a half, 16 blocks.
 * test_glow_mix_*                    glow_mix_kernel: the stride loop behind the 2048-block grid cap (rows * 40 > 524 288: 13 108

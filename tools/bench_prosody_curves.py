@@ -7,8 +7,10 @@ fixture weights, --precision, default bf16, no vocoder):
            utterance's second word) and the statistics of utterances and spans; the time includes turning the Spans into the
            packed table on the host (prosody.resolve_curves), which is also reported on its own;
   scales   the control step is tts_control_and_regulate_v with the same per-utterance scales, on the same commit;
+  scalars  the control step is the scalar tts_control_and_regulate with (1.02, 1.04, 0.96, 1.0), on the same commit;
   parent   the same as ``scales`` in a checkout of the parent commit built beside this one (--parent-root), where the curves do
-           not exist: what stage A cost before.
+           not exist: what stage A cost before.  --parent-entries scalars,scales,curves: a parent that has all three ways runs
+           all three (keys parent_scalars, parent, parent_curves).
 
 Every figure is a host clock around one stage A that ends in a device synchronise, --reps times after --warmup, the entries of one
 process in alternation; this tree and the parent run in fresh child processes, alternating, --rounds times each, because two
@@ -58,6 +60,8 @@ def stage_worker(args):
     scales = [[1.0 + 0.01 * (u % 5) for u in range(B)], [1.0 + 0.02 * (u % 3) for u in range(B)], [1.0 - 0.02 * (u % 4) for u in range(B)], 1.0]
     st = pipe._stream()
     ways = {"scales": lambda: pipe._stage_a(packed, *scales, st)}
+    if "scalars" in args.entries:  # one set of scalars for the batch: tts_control_and_regulate
+        ways["scalars"] = lambda: pipe._stage_a(packed, 1.02, 1.04, 0.96, 1.0, st)
     if "curves" in args.entries:
         curves = []
         for f in feats:  # one Span per utterance: its second word (the first if it has one word only)
@@ -164,6 +168,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sweep-steps", type=int, default=7)
     ap.add_argument("--parent-root", default=None, help="a built checkout of the parent commit")
+    ap.add_argument("--parent-entries", default="scales", help="the ways the parent has: scalars,scales,curves (keys parent_scalars, parent, parent_curves)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--root", default=os.path.dirname(HERE), help=argparse.SUPPRESS)
@@ -183,7 +188,7 @@ def main():
 
     pooled, rounds, frames, gpu, host = {}, {}, {}, None, []
     for _ in range(args.rounds):  # alternating processes: this tree, the parent, this tree, ...
-        for name, root, entries in (("this", os.path.dirname(HERE), "scales,curves"), ("parent", args.parent_root, "scales")):
+        for name, root, entries in (("this", os.path.dirname(HERE), "scalars,scales,curves"), ("parent", args.parent_root, args.parent_entries)):
             if root is None:
                 continue
             res = child(root, entries)
@@ -191,7 +196,7 @@ def main():
             if res.get("resolve_curves_host_ms") is not None:
                 host.append(res["resolve_curves_host_ms"])
             for k, v in res["ms"].items():
-                key = k if name == "this" else "parent"
+                key = k if name == "this" else "parent" if k == "scales" else "parent_" + k
                 pooled.setdefault(key, []).extend(v)
                 rounds.setdefault(key, []).append(_summary(v)["median"])
                 frames[key] = res["frames"][k]
