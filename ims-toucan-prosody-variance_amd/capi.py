@@ -275,6 +275,20 @@ DTW_MAX_FRAMES, DTW_LDS_BP_BYTES, DTW_N_SUMS = 4096, 40960, 12  # TTS_DTW_MAX_FR
 # the columns of tts_dtw_path_sums, in the order of the header's TTS_DTW_SUM_* indices
 DTW_SUM_COLUMNS = ("mcd", "diag", "vv", "sq_hz", "sq_cents", "x", "y", "xx", "yy", "xy", "gross", "vuv")
 
+class TtsPronUtt(C.Structure):
+    _fields_ = [("frame_begin", _i), ("n_frames", _i), ("ref_begin", _i), ("n_ref", _i), ("scratch_off", _l)]
+
+
+# symbol -> (restype, argtypes); mirrors include/toucan_pronunciation.h (CTC decoders, edit distance, posteriors over the forced alignment: csrc/pronunciation.hip) one to one
+PRONUNCIATION_PROTOTYPES = {
+    "tts_ctc_best_path": (C.c_int, [_p, _i, _i, _i, _i, _p, C.POINTER(TtsPronUtt), _p, _i, _p, _p, _p, _p, _p, _p]),
+    "tts_ctc_beam_search": (C.c_int, [_p, _i, _i, _i, _i, _p, C.POINTER(TtsPronUtt), _p, _i, _i, _p, _l, _p, _p, _p, _p]),
+    "tts_edit_distance": (C.c_int, [_p, _i, _p, _i, _p, C.POINTER(TtsPronUtt), _p, _i, _p, _l, _i, _p, _p, _p, _p]),
+    "tts_phone_posteriors": (C.c_int, [_p, _i, _i, _i, _p, _p, _i, C.POINTER(TtsPronUtt), _p, _i, _p, _p]),
+}
+# include/toucan_pronunciation.h TTS_PRON_MAX_SYMBOLS, TTS_BEAM_MAX, TTS_CTC_SCAN_BLOCK, TTS_EDIT_MAX_REF, TTS_EDIT_MAX_HYP, TTS_EDIT_LDS_BP_BYTES, TTS_PHONE_COLUMNS
+PRON_MAX_SYMBOLS, BEAM_MAX, CTC_SCAN_BLOCK, EDIT_MAX_REF, EDIT_MAX_HYP, EDIT_LDS_BP_BYTES, PHONE_COLUMNS = 256, 32, 256, 2048, 4096, 28672, 4
+
 # symbol -> (restype, argtypes); mirrors include/toucan_loudness.h (BS.1770 loudness and the gain to a target: csrc/loudness.hip) one to one
 LOUDNESS_PROTOTYPES = {
     "tts_loudness_tile_segments": (C.c_int, []),
@@ -320,7 +334,7 @@ def lib():
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
             list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()) + \
-            list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()):
+            list(PRONUNCIATION_PROTOTYPES.items()) + list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -104,6 +104,44 @@ def _begins(counts):
     return [int(b) for b in np.concatenate([[0], np.cumsum(counts)[:-1]])] if len(counts) else []
 
 
+def waves_to_16k(owner, waves, srs, names, tracked=False):
+    """Mono float32 waves at their rates -> at 16 kHz (device resampler), each divided by its peak: the one route from a wave to
+    the 16 kHz front ends (SpeechComparator, pronunciation.PronunciationChecker).  owner: holds ``device`` and ``_resampler`` (None
+    until a rate other than 16 kHz asks for it).  names: what a refusal calls each wave.  Everything that can be refused is refused
+    before the first launch."""
+    from . import pitch, resample
+    out, n16 = [], []
+    for p, (w, sr) in enumerate(zip(waves, srs)):
+        x = np.asarray(w, dtype=np.float32)
+        x = x.mean(axis=1) if x.ndim == 2 else x.reshape(-1)
+        name = names[p]
+        if not np.isfinite(x).all():
+            raise ValueError(f"{name}: the wave holds a sample that is not finite")
+        n = len(x) if sr == SR else resample.out_length(len(x), sr, SR)
+        if n < MIN_STFT_SAMPLES:
+            raise ValueError(f"{name}: {n} samples at 16 kHz are too short for the centred STFT ({MIN_STFT_SAMPLES} at least)")
+        if 1 + n // HOP > MAX_FRAMES:
+            raise ValueError(f"{name}: {1 + n // HOP} frames are past the cap of {MAX_FRAMES} ({MAX_FRAMES * HOP / SR:.0f} s)")
+        if tracked and n < pitch.MIN_SAMPLES:
+            raise ValueError(f"{name}: {n} samples at 16 kHz are too short for the pitch tracker ({pitch.MIN_SAMPLES} at least)")
+        out.append(np.ascontiguousarray(x, dtype=np.float32))
+        n16.append(n)
+    for sr in sorted({int(s) for s in srs if s != SR}):  # one launch per rate
+        which = [p for p, s in enumerate(srs) if s == sr]
+        if owner._resampler is None:
+            owner._resampler = resample.Resampler(owner.device)
+        packed = torch.from_numpy(np.concatenate([out[p] for p in which])).to(owner.device)
+        y, spans = owner._resampler.resample(packed, list(zip(_begins([len(out[p]) for p in which]), [len(out[p]) for p in which])), sr, SR)
+        y = y.cpu().numpy()
+        for p, (b, n) in zip(which, spans):
+            out[p] = y[b:b + n].copy()
+    for p, x in enumerate(out):
+        peak = np.abs(x).max()
+        if peak > 0:
+            out[p] = x / peak
+    return out
+
+
 class SpeechComparator:
     """``compare(waves_a, waves_b, sr_a)``: the measures for every pair, b being the reference side; ``cepstra``, ``dtw`` and
     ``path_sums`` are its three stages on their own."""
@@ -245,39 +283,7 @@ class SpeechComparator:
 
     # ---- waves --------------------------------------------------------------------------------------------------------------
     def _to_16k(self, waves, srs, tracked, side):
-        """Mono float32 waves at their rates -> at 16 kHz (device resampler), each divided by its peak.  Everything that can be
-        refused is refused before the first launch."""
-        from . import pitch, resample
-        out, n16 = [], []
-        for p, (w, sr) in enumerate(zip(waves, srs)):
-            x = np.asarray(w, dtype=np.float32)
-            x = x.mean(axis=1) if x.ndim == 2 else x.reshape(-1)
-            name = f"pair {p}, side {side}"
-            if not np.isfinite(x).all():
-                raise ValueError(f"{name}: the wave holds a sample that is not finite")
-            n = len(x) if sr == SR else resample.out_length(len(x), sr, SR)
-            if n < MIN_STFT_SAMPLES:
-                raise ValueError(f"{name}: {n} samples at 16 kHz are too short for the centred STFT ({MIN_STFT_SAMPLES} at least)")
-            if 1 + n // HOP > MAX_FRAMES:
-                raise ValueError(f"{name}: {1 + n // HOP} frames are past the cap of {MAX_FRAMES} ({MAX_FRAMES * HOP / SR:.0f} s)")
-            if tracked and n < pitch.MIN_SAMPLES:
-                raise ValueError(f"{name}: {n} samples at 16 kHz are too short for the pitch tracker ({pitch.MIN_SAMPLES} at least)")
-            out.append(np.ascontiguousarray(x, dtype=np.float32))
-            n16.append(n)
-        for sr in sorted({int(s) for s in srs if s != SR}):  # one launch per rate
-            which = [p for p, s in enumerate(srs) if s == sr]
-            if self._resampler is None:
-                self._resampler = resample.Resampler(self.device)
-            packed = torch.from_numpy(np.concatenate([out[p] for p in which])).to(self.device)
-            y, spans = self._resampler.resample(packed, list(zip(_begins([len(out[p]) for p in which]), [len(out[p]) for p in which])), sr, SR)
-            y = y.cpu().numpy()
-            for p, (b, n) in zip(which, spans):
-                out[p] = y[b:b + n].copy()
-        for p, x in enumerate(out):
-            peak = np.abs(x).max()
-            if peak > 0:
-                out[p] = x / peak
-        return out
+        return waves_to_16k(self, waves, srs, [f"pair {p}, side {side}" for p in range(len(waves))], tracked)
 
     def _tracks(self, f0, a16, b16, frames_a, frames_b):
         """The f0 keyword -> (packed f0 of side a, of side b) on the device, laid onto the mel frames, or (None, None)."""

@@ -13,7 +13,9 @@ script written against the reference (run_text_to_file_reader.py:8-16) works unc
   a scalar or one value per utterance), ``synthesize_grid`` (one text over a grid of prosody scales, with the statistics of what
   each scale did), ``prosody_curves=`` / ``curves=`` (per-phoneme prosody curves: stress one word, prosody.emphasis),
   ``evaluate_against_recordings`` (synthesise and measure against recordings of the same sentences: MCD along a DTW path and
-  the F0 errors, compare.py), ``loudness=`` / ``peak_ceiling=`` (every utterance brought to a target integrated loudness after
+  the F0 errors, compare.py), ``check_pronunciation`` / ``synthesize_grid(check_pronunciation=True)`` (synthesise and ask the aligner
+  whether the waveform still says the text, without a recording: phoneme error rate of the decoded CTC posteriors and per-phoneme
+  goodness of pronunciation over the forced alignment, pronunciation.py), ``loudness=`` / ``peak_ceiling=`` (every utterance brought to a target integrated loudness after
   ITU-R BS.1770 under a sample-peak ceiling, on the device: loudness.py), ``speech_level=`` (the same for the active
   speech level after ITU-T P.56: activity.py), ``trim_silence=`` on ``set_utterance_embedding``
 
@@ -495,6 +497,49 @@ class ToucanTTSInterface(torch.nn.Module):
                 r.update(synth=s, recording=w, recording_sr=sr)
         return results
 
+    def _checker(self):
+        """The pronunciation checker, built on first use from the aligner checkpoint the cloner loads (Models/Aligner/aligner.pt)."""
+        if getattr(self, "_checker_obj", None) is None:
+            from . import pronunciation
+            path = os.path.join(MODELS_DIR, "Aligner", "aligner.pt")
+            if not os.path.exists(path):
+                raise FileNotFoundError(f"{path}: aligner checkpoint not found (offline, write the fixture one with "
+                                        f"ims_toucan_prosody_variance_amd.interface.write_fixture_aligner_checkpoint)")
+            sd = torch.load(path, map_location="cpu", weights_only=True)["asr_model"]
+            self._checker_obj = pronunciation.PronunciationChecker(sd, self.device)
+        return self._checker_obj
+
+    def check_pronunciation(self, texts, input_is_phones=True, beam=8, ignore_ids=(), keep_waves=False, **synthesis_keywords):
+        """Additive API: synthesise ``texts`` as one batch (``synthesize_batch`` with ``synthesis_keywords``: prosody scales, curves,
+        gold prosody, ``z_noise``, ``utterance_embeddings``) and ask the aligner whether each waveform still says its text, without
+        any recording (pronunciation.PronunciationChecker.check): the phoneme error rate of the decoded
+        phonemes (``beam``: the width of the CTC prefix beam search, 0 for the greedy best path) with the substituted, deleted and
+        inserted phonemes, the CTC loss, and per phoneme of the text its frames in the forced alignment, mean log-posterior,
+        goodness of pronunciation and frame accuracy.  ``ignore_ids``: aligner ids left out of both the text and the decode
+        (silences, punctuation).  -> one dict per text (``check_logits`` documents it); with ``keep_waves`` it also holds "synth"
+        (float32, 24 kHz).  The numbers are the aligner's opinion, meant for comparing settings of one sentence against each
+        other, not an absolute intelligibility score.  ValueError for ``distributed=True``, for ``sample_rate`` / ``pcm16`` (the
+        check takes the 24 kHz float waveform), for ``loudness`` and ``speech_level`` (the wave is divided by its peak anyway),
+        and what ``check`` refuses."""
+        if synthesis_keywords.get("distributed"):
+            raise ValueError("check_pronunciation is not available with distributed=True: the check runs on one device")
+        if synthesis_keywords.get("sample_rate") is not None or synthesis_keywords.get("pcm16"):
+            raise ValueError("check_pronunciation checks the 24 kHz float waveform: sample_rate / pcm16 do not apply")
+        if synthesis_keywords.get("loudness") is not None:
+            raise ValueError("check_pronunciation divides the wave by its peak before it checks it: loudness does not apply")
+        if synthesis_keywords.get("speech_level") is not None:
+            raise ValueError("check_pronunciation divides the wave by its peak before it checks it: speech_level does not apply")
+        from . import pronunciation
+        pronunciation.check_beam(beam)
+        pronunciation.drop_mask(ignore_ids)
+        feats = [t if torch.is_tensor(t) else self.text2phone.string_to_tensor(t, input_phonemes=input_is_phones) for t in texts]
+        synth = [w.float().cpu().numpy() for w in self.synthesize_batch(feats, input_is_phones=input_is_phones, **synthesis_keywords)]
+        results = self._checker().check([f.float().cpu().numpy() for f in feats], synth, self.SAMPLE_RATE, beam=beam, ignore_ids=ignore_ids)
+        if keep_waves:
+            for r, w in zip(results, synth):
+                r["synth"] = w
+        return results
+
     def synthesize_ensemble(self, text, utterance_embeddings, durations=None, pitch=None, energy=None, input_is_phones=True, z_noise=None,
                             sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None):
         """Several voices speaking one text with the same prosody, averaged (UtteranceCloner.py:166-194's ensemble) - as ONE batch
@@ -520,7 +565,7 @@ class ToucanTTSInterface(torch.nn.Module):
     def synthesize_grid(self, text, duration_scaling_factors=(1.0,), pitch_variance_scales=(1.0,), energy_variance_scales=(1.0,),
                         pause_duration_scaling_factors=(1.0,), input_is_phones=True, utterance_embedding=None, durations=None, pitch=None,
                         energy=None, z_noise=None, sample_rate=None, pcm16=False, curves=None, loudness=None, peak_ceiling=-1.0,
-                        speech_level=None):
+                        speech_level=None, check_pronunciation=False, beam=8):
         """Additive API: ONE text (a phoneme string, or its [L, 62] feature tensor) at every combination of the four tuples of prosody scales - the Cartesian product in row-major
         order of the tuples as listed (the pause factor varies fastest) - synthesised as ragged batches of at most MAX_FILE_BATCH
         variants with per-utterance scales instead of one pass per setting.  Returns one dict per variant, in that order:
@@ -540,8 +585,15 @@ class ToucanTTSInterface(torch.nn.Module):
         ``loudness``, its float64 [8] row of statistics on the device; ``self.last_loudness`` holds all rows, in variant order.
         ``speech_level`` (as in ``synthesize_batch``) likewise: every dict gains ``speech_activity`` = (its stats row [8], its runs
         [64, 2], its counts [16]) - what ``pause_duration_scaling_factor`` really did to the pauses can be read from the runs
-        (``activity.pauses``) - and ``self.last_speech_activity`` holds all rows, in variant order."""
+        (``activity.pauses``) - and ``self.last_speech_activity`` holds all rows, in variant order.
+        ``check_pronunciation`` / ``beam``: every dict gains ``pronunciation``, what ``check_pronunciation`` returns for that variant
+        alone (the 24 kHz float waveform as synthesised, before ``loudness`` / ``speech_level`` / ``sample_rate``): phoneme error rate
+        and minimum goodness of pronunciation against the scales or the emphasised word - how far a knob goes before the words
+        break, in the aligner's opinion."""
         self._check_output_format(sample_rate, pcm16)
+        if check_pronunciation:
+            from . import pronunciation
+            pronunciation.check_beam(beam)
         normalise = self._check_loudness(loudness, peak_ceiling)
         level = self._check_speech_level(loudness, speech_level, peak_ceiling)
         rows, activity_rows = [], []
@@ -571,6 +623,10 @@ class ToucanTTSInterface(torch.nn.Module):
                                                          durations=rep(durations), pitch=rep(pitch), energy=rep(energy),
                                                          **{name: [v[k] for v in chunk] for k, name in enumerate(prosody.KNOBS)}, **kw)
                 before, after = self.last_prosody_stats
+                checked = None
+                if check_pronunciation:
+                    host24 = wav24.float().cpu().numpy()
+                    checked = self._checker().check([phones.float().cpu().numpy()] * n, [host24[b:b + m] for b, m in spans24], self.SAMPLE_RATE, beam=beam)
                 wav24 = self._normalize(wav24, spans24, loudness, peak_ceiling, speech_level)
                 if normalise:
                     rows.append(self.last_loudness)
@@ -580,6 +636,8 @@ class ToucanTTSInterface(torch.nn.Module):
                 for i, scales in enumerate(chunk):
                     results.append({"scales": scales, "wave": wav[spans[i][0]:spans[i][0] + spans[i][1]], "frames": int(spans24[i][1]) // 384,
                                     "stats_before": before[i], "stats_after": after[i]})
+                    if checked is not None:
+                        results[-1]["pronunciation"] = checked[i]
                     if normalise:
                         results[-1]["loudness"] = rows[-1][i]
                     if level:
