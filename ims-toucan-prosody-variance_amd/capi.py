@@ -309,6 +309,17 @@ ACTIVITY_PROTOTYPES = {
 # include/toucan_activity.h TTS_ACTIVITY_MIN_RATE, _MAX_RATE, _COLUMNS, _THRESHOLDS, _COUNTS, _TABLE_DOUBLES
 ACTIVITY_MIN_RATE, ACTIVITY_MAX_RATE, ACTIVITY_N_COLUMNS, ACTIVITY_THRESHOLDS, ACTIVITY_COUNTS, ACTIVITY_TABLE_DOUBLES = 8000, 192000, 8, 15, 16, 6
 
+# symbol -> (restype, argtypes); mirrors include/toucan_truepeak.h (true peak, loudness range, the gain under a true-peak ceiling: csrc/truepeak.hip) one to one
+TRUEPEAK_PROTOTYPES = {
+    "tts_truepeak_tile_samples": (C.c_int, []),
+    "tts_true_peak": (C.c_int, [_p, _l, _p, _p, _i, _l, _p, _i, _p, _p, _p]),
+    "tts_loudness_range": (C.c_int, [_p, _p, _p, _l, _p, _i, _i, _l, _p, _p, _p]),
+    "tts_truepeak_gain": (C.c_int, [_p, _l, _p, _p, _i, _p, _i, _p, C.c_double, _p, _p, _p, _p]),
+    "tts_limit_true_peak": (C.c_int, [_p, _l, _p, _p, _i, _l, _i, _p, _i, _p, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p]),
+}
+# include/toucan_truepeak.h TTS_TRUEPEAK_TAPS, _HALF_WIDTH, _MAX_STEPS, _TILED_ROUNDS, _SHORT_TERM_SEGMENTS, TTS_DELIVERY_COLUMNS, TTS_LIMITER_COLUMNS
+TRUEPEAK_TAPS, TRUEPEAK_HALF_WIDTH, TRUEPEAK_MAX_STEPS, TRUEPEAK_TILED_ROUNDS, TRUEPEAK_SHORT_TERM_SEGMENTS, DELIVERY_N_COLUMNS, LIMITER_N_COLUMNS = 15, 7, 128, 3, 30, 12, 8
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -334,7 +345,8 @@ def lib():
     for name, (res, args) in list(PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(SCORE_PROTOTYPES.items()) + \
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
             list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()) + \
-            list(PRONUNCIATION_PROTOTYPES.items()) + list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()):
+            list(PRONUNCIATION_PROTOTYPES.items()) + list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()) + \
+            list(TRUEPEAK_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -16,7 +16,8 @@ script written against the reference (run_text_to_file_reader.py:8-16) works unc
   the F0 errors, compare.py), ``check_pronunciation`` / ``synthesize_grid(check_pronunciation=True)`` (synthesise and ask the aligner
   whether the waveform still says the text, without a recording: phoneme error rate of the decoded CTC posteriors and per-phoneme
   goodness of pronunciation over the forced alignment, pronunciation.py), ``loudness=`` / ``peak_ceiling=`` (every utterance brought to a target integrated loudness after
-  ITU-R BS.1770 under a sample-peak ceiling, on the device: loudness.py), ``speech_level=`` (the same for the active
+  ITU-R BS.1770 under a sample-peak ceiling, on the device: loudness.py; ``true_peak_ceiling=`` / ``limiter=`` add a true-peak
+  ceiling and a look-ahead limiter: truepeak.py), ``speech_level=`` (the same for the active
   speech level after ITU-T P.56: activity.py), ``trim_silence=`` on ``set_utterance_embedding``
 
 * ``set_utterance_embedding(path)`` (:103-114): reference audio -> log-mel -> GST style embedding on the GPU (style.py)
@@ -167,6 +168,7 @@ class ToucanTTSInterface(torch.nn.Module):
         self._style = None
         self.last_prosody_stats = None  # (before, after) of the last batch that took per-utterance prosody scales or curves
         self.last_prosody_span_stats = None  # per utterance (before, after) of its Spans, of the last batch that took prosody curves
+        self.last_delivery = None  # float64 [B, 8] on the device (truepeak.DELIVERY_COLUMNS) of the last call that took true_peak_ceiling= / limiter=
         self.last_loudness = None  # float64 [B, 8] on the device (loudness.LOUDNESS_COLUMNS) of the last call that took loudness=
         self.last_speech_activity = None  # (stats [B, 8], runs [B, 64, 2], counts [B, 16]) on the device of the last call that took speech_level=
 
@@ -239,17 +241,21 @@ class ToucanTTSInterface(torch.nn.Module):
                 prosody_curves=None,
                 loudness=None,
                 peak_ceiling=-1.0,
-                speech_level=None):
+                speech_level=None,
+                true_peak_ceiling=None,
+                limiter=False):
         """The reference's signature (ToucanTTSInterface.py:132-143) plus additive keywords.  ``z_noise`` [80, T]: the PostFlow
         noise 0.8 N(0,1) the reference draws inside the model (Glow.py:363), so that a call can be reproduced and checked
         against the oracle; None draws it on the device.  ``sample_rate`` / ``pcm16``: the waveform at another rate than 24 kHz
         and / or as int16, converted on the device (resample.py); the figure of ``view`` keeps drawing the 24 kHz wave.
         ``prosody_curves``: this utterance's per-phoneme curves, an [L, 5] array or a list of ``prosody.Span`` (as one entry of
         ``synthesize_batch``'s keyword, documented there); None is the call as it was.  ``loudness`` / ``peak_ceiling``: as in
-        ``synthesize_batch``; the figure of ``view`` then draws the normalised 24 kHz wave.  ``speech_level``: as in ``synthesize_batch``."""
+        ``synthesize_batch``; the figure of ``view`` then draws the normalised 24 kHz wave.  ``speech_level``, ``true_peak_ceiling`` / ``limiter``: as in
+        ``synthesize_batch``."""
         self._check_output_format(sample_rate, pcm16)
         self._check_loudness(loudness, peak_ceiling)
         self._check_speech_level(loudness, speech_level, peak_ceiling)
+        self._check_delivery(loudness, speech_level, true_peak_ceiling, limiter)
         with torch.inference_mode():
             phones = self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
             curves = {} if prosody_curves is None else dict(prosody_curves=[prosody_curves])
@@ -261,7 +267,7 @@ class ToucanTTSInterface(torch.nn.Module):
                                                    duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
                                                    energy_variance_scale=energy_variance_scale,
                                                    pause_duration_scaling_factor=pause_duration_scaling_factor, **curves)
-            wav24 = self._normalize(wav24, spans, loudness, peak_ceiling, speech_level)
+            wav24 = self._normalize(wav24, spans, loudness, peak_ceiling, speech_level, true_peak_ceiling, limiter)
             wav, out_spans = self._convert(wav24, spans, sample_rate, pcm16)
             wavs = [wav[b:b + n] for b, n in out_spans]
         if view or return_plot_as_filepath:  # ToucanTTSInterface.py:171-226 (matplotlib only: plotting.py)
@@ -297,9 +303,10 @@ class ToucanTTSInterface(torch.nn.Module):
         self.last_prosody_span_stats = out.get("prosody_span_stats")
         return wav, list(zip(rag.begins, rag.lengths))
 
-    def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None, **kw):
+    def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None,
+                    true_peak_ceiling=None, limiter=False, **kw):
         wav, spans = self._synthesize_packed(phones, embs, langs, z_noise=z_noise, **kw)
-        wav = self._normalize(wav, spans, loudness, peak_ceiling, speech_level)
+        wav = self._normalize(wav, spans, loudness, peak_ceiling, speech_level, true_peak_ceiling, limiter)
         wav, spans = self._convert(wav, spans, sample_rate, pcm16)
         return [wav[b:b + n] for b, n in spans]
 
@@ -355,23 +362,52 @@ class ToucanTTSInterface(torch.nn.Module):
         ac.check_target(speech_level, peak_ceiling)
         return True
 
+    @staticmethod
+    def _check_delivery(loudness, speech_level, true_peak_ceiling, limiter):
+        """ValueError for ``true_peak_ceiling`` or ``limiter`` without ``loudness`` or together with ``speech_level``, for a ceiling
+        that is not finite or above 0 dBTP; True if the normalisation is to hold a true-peak ceiling at all."""
+        if true_peak_ceiling is None and not limiter:
+            return False
+        if speech_level is not None:
+            raise ValueError("true_peak_ceiling and limiter belong to the loudness normalisation: they do not combine with speech_level")
+        if loudness is None:
+            raise ValueError("true_peak_ceiling and limiter belong to the loudness normalisation: give loudness= as well")
+        from . import truepeak as tp
+        if true_peak_ceiling is not None:
+            tp.check_ceiling(true_peak_ceiling)
+        return True
+
+    def _delivery(self):
+        if getattr(self, "_delivery_obj", None) is None:
+            from . import truepeak as tp
+            self._delivery_obj = tp.DeliveryMeter(self.device, self._meter())
+        return self._delivery_obj
+
     def _activity(self):
         if getattr(self, "_activity_obj", None) is None:
             from . import activity as ac
             self._activity_obj = ac.SpeechActivity(self.device)
         return self._activity_obj
 
-    def _normalize(self, wav, spans, loudness, peak_ceiling, speech_level=None):
+    def _normalize(self, wav, spans, loudness, peak_ceiling, speech_level=None, true_peak_ceiling=None, limiter=False):
         """The packed 24 kHz waveform with every utterance at ``loudness`` LUFS (ITU-R BS.1770 integrated loudness) or at the
         active speech level ``speech_level`` dB (ITU-T P.56), or as close as the sample-peak ceiling ``peak_ceiling`` dBFS allows,
         measured and scaled on the device behind the vocoder on its stream; ``self.last_loudness`` or
-        ``self.last_speech_activity`` gets the statistics.  Both None returns the waveform as it came, without a launch."""
+        ``self.last_speech_activity`` gets the statistics.  Both None returns the waveform as it came, without a launch.  With
+        ``true_peak_ceiling`` (dBTP; None with ``limiter`` alone: -1) the loudness normalisation also holds the true peak under
+        that ceiling - by its one gain, or with ``limiter`` by a look-ahead limiter behind the gain to the target (truepeak.py) -
+        and ``self.last_delivery`` gets the statistics of the result."""
+        delivery = self._check_delivery(loudness, speech_level, true_peak_ceiling, limiter)
         if self._check_speech_level(loudness, speech_level, peak_ceiling):
             meter = self._activity()
             wav, stats = meter.normalize(wav.contiguous(), spans, self.SAMPLE_RATE, speech_level, peak_ceiling)
             self.last_speech_activity = (stats, meter.last_runs, meter.last_counts)
             return wav
         if not self._check_loudness(loudness, peak_ceiling):
+            return wav
+        if delivery:
+            wav, self.last_loudness, self.last_delivery = self._delivery().normalize(
+                wav.contiguous(), spans, self.SAMPLE_RATE, loudness, peak_ceiling, -1.0 if true_peak_ceiling is None else true_peak_ceiling, bool(limiter))
             return wav
         wav, self.last_loudness = self._meter().normalize(wav.contiguous(), spans, self.SAMPLE_RATE, loudness, peak_ceiling)
         return wav
@@ -385,7 +421,7 @@ class ToucanTTSInterface(torch.nn.Module):
     def synthesize_batch(self, texts, input_is_phones=True, utterance_embeddings=None, z_noise=None, durations=None, pitch=None,
                          energy=None, duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
                          pause_duration_scaling_factor=1.0, distributed=False, sample_rate=None, pcm16=False, prosody_curves=None,
-                         loudness=None, peak_ceiling=-1.0, speech_level=None):
+                         loudness=None, peak_ceiling=-1.0, speech_level=None, true_peak_ceiling=None, limiter=False):
         """Additive API: a ragged batch in one pass; each utterance equals the reference run on it alone (16-bit configurations: bit
         for bit whatever the batch; fp32: durations / pitch / energy bit for bit, the mel to fp32 rounding order - DESIGN.md section 4).
         texts: phoneme strings (or [L,62] feature tensors).  durations / pitch / energy: optional per-utterance gold prosody (the
@@ -415,7 +451,7 @@ class ToucanTTSInterface(torch.nn.Module):
         utterance's integrated loudness after ITU-R BS.1770-4 (K-weighting, 400 ms blocks, absolute gate at -70 LUFS, relative gate
         at -10 LU) is measured at 24 kHz on the device and the utterance scaled by one gain to the target, before the conversion of
         ``sample_rate`` / ``pcm16``; ``peak_ceiling`` (dBFS, at most 0) limits the gain so that no SAMPLE exceeds it - a sample peak,
-        not an oversampled true peak.  An utterance without a loudness (shorter than 400 ms, or silent) keeps its bits.
+        not an oversampled true peak (``true_peak_ceiling`` below adds that).  An utterance without a loudness (shorter than 400 ms, or silent) keeps its bits.
         ``self.last_loudness``: float64 [B, 8] on the device, columns ``loudness.LOUDNESS_COLUMNS`` (the loudness found, the peak,
         the blocks and what each gate kept, the loudest block, the gain applied, the loudness reached).  ValueError for a target or
         ceiling that is not finite, a ceiling above 0, and with ``distributed=True``.
@@ -426,13 +462,26 @@ class ToucanTTSInterface(torch.nn.Module):
         ``self.last_speech_activity`` = (stats float64 [B, 8], columns ``activity.ACTIVITY_COLUMNS``: both levels, the activity
         factor, the threshold, the bounds of the speech in samples, the gain, the level reached; runs int64 [B, 64, 2]: the runs of
         speech, ``activity.pauses`` gives the pauses between them; counts int64 [B, 16]: the active samples per threshold and the
-        number of runs), all on the device.  ValueError together with ``loudness`` and wherever ``loudness`` raises one."""
+        number of runs), all on the device.  ValueError together with ``loudness`` and wherever ``loudness`` raises one.
+        ``true_peak_ceiling`` / ``limiter`` (with ``loudness``; None and False are the call as it was: the same launches, the same
+        bits): a ceiling in dBTP, at most 0, for the TRUE peak after ITU-R BS.1770-4 Annex 2 - the 24 kHz utterance oversampled 4x
+        on the device (truepeak.py) - which the one gain then respects as well as ``peak_ceiling``: the
+        meter's own reading of the result is at or under it.  A peaky utterance then ends below the target; ``limiter=True``
+        instead applies the gain to the target and runs a look-ahead limiter (2 ms, feed-forward) that holds samples and true
+        peak under the lower of the two ceilings (``true_peak_ceiling=None`` then means -1).  ``self.last_delivery``: float64
+        [B, 8] on the device, columns ``truepeak.DELIVERY_COLUMNS`` (true peak, the same in dBTP, sample peak, largest short-term
+        loudness, loudness range with its two percentiles, short-term blocks kept) of the waveforms as returned at 24 kHz;
+        ``self.last_loudness`` holds the gain and the loudness reached (measured again behind the limiter).  ValueError without
+        ``loudness``, together with ``speech_level``, for a ceiling that is not finite or above 0, and with ``distributed=True``."""
+        if distributed and (true_peak_ceiling is not None or limiter):
+            raise ValueError("true_peak_ceiling / limiter are not available with distributed=True: the sharded exchange carries the waveforms as synthesised")
         if distributed and loudness is not None:
             raise ValueError("loudness is not available with distributed=True: the sharded exchange carries the waveforms as synthesised")
         if distributed and speech_level is not None:
             raise ValueError("speech_level is not available with distributed=True: the sharded exchange carries the waveforms as synthesised")
         self._check_loudness(loudness, peak_ceiling)
         self._check_speech_level(loudness, speech_level, peak_ceiling)
+        self._check_delivery(loudness, speech_level, true_peak_ceiling, limiter)
         if distributed and (sample_rate is not None or pcm16):
             raise ValueError("sample_rate / pcm16 are not available with distributed=True: the sharded exchange carries 24 kHz float32")
         self._check_output_format(sample_rate, pcm16)
@@ -453,7 +502,7 @@ class ToucanTTSInterface(torch.nn.Module):
             with torch.inference_mode():
                 return self._synthesize(feats, embs, [self._lang()] * len(feats), z_noise=z_noise, durations=durations, pitch=pitch,
                                         energy=energy, sample_rate=sample_rate, pcm16=pcm16, loudness=loudness, peak_ceiling=peak_ceiling,
-                                        speech_level=speech_level, **kw)
+                                        speech_level=speech_level, true_peak_ceiling=true_peak_ceiling, limiter=limiter, **kw)
         from . import distributed as dd
         return dd.synthesize_sharded(self, feats, embs, z_noise, durations, pitch, energy, kw)
 
@@ -541,14 +590,17 @@ class ToucanTTSInterface(torch.nn.Module):
         return results
 
     def synthesize_ensemble(self, text, utterance_embeddings, durations=None, pitch=None, energy=None, input_is_phones=True, z_noise=None,
-                            sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None):
+                            sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None, true_peak_ceiling=None,
+                            limiter=False):
         """Several voices speaking one text with the same prosody, averaged (UtteranceCloner.py:166-194's ensemble) - as ONE batch
         over the voices instead of a loop that swaps the default embedding.  Without gold durations the voices may predict
         different lengths; the mean is then taken over the common prefix.  ``sample_rate`` / ``pcm16`` convert the 24 kHz mean;
-        ``loudness`` / ``peak_ceiling`` or ``speech_level`` (as in ``synthesize_batch``) normalise the mean, before that conversion."""
+        ``loudness`` / ``peak_ceiling`` (with ``true_peak_ceiling`` / ``limiter``) or ``speech_level`` (as in ``synthesize_batch``)
+        normalise the mean, before that conversion."""
         convert = self._check_output_format(sample_rate, pcm16)
         self._check_loudness(loudness, peak_ceiling)
         self._check_speech_level(loudness, speech_level, peak_ceiling)
+        self._check_delivery(loudness, speech_level, true_peak_ceiling, limiter)
         n = len(utterance_embeddings)
         rep = lambda v: None if v is None else [v] * n
         waves = self.synthesize_batch([text] * n, input_is_phones=input_is_phones, utterance_embeddings=list(utterance_embeddings),
@@ -556,7 +608,7 @@ class ToucanTTSInterface(torch.nn.Module):
         m = min(w.numel() for w in waves)
         mean = torch.stack([w[:m] for w in waves]).mean(dim=0)
         with torch.inference_mode():
-            mean = self._normalize(mean, [(0, m)], loudness, peak_ceiling, speech_level)
+            mean = self._normalize(mean, [(0, m)], loudness, peak_ceiling, speech_level, true_peak_ceiling, limiter)
         if not convert:
             return mean
         wav, spans = self._convert(mean, [(0, m)], sample_rate, pcm16)
@@ -565,7 +617,7 @@ class ToucanTTSInterface(torch.nn.Module):
     def synthesize_grid(self, text, duration_scaling_factors=(1.0,), pitch_variance_scales=(1.0,), energy_variance_scales=(1.0,),
                         pause_duration_scaling_factors=(1.0,), input_is_phones=True, utterance_embedding=None, durations=None, pitch=None,
                         energy=None, z_noise=None, sample_rate=None, pcm16=False, curves=None, loudness=None, peak_ceiling=-1.0,
-                        speech_level=None, check_pronunciation=False, beam=8):
+                        speech_level=None, check_pronunciation=False, beam=8, true_peak_ceiling=None, limiter=False):
         """Additive API: ONE text (a phoneme string, or its [L, 62] feature tensor) at every combination of the four tuples of prosody scales - the Cartesian product in row-major
         order of the tuples as listed (the pause factor varies fastest) - synthesised as ragged batches of at most MAX_FILE_BATCH
         variants with per-utterance scales instead of one pass per setting.  Returns one dict per variant, in that order:
@@ -583,6 +635,8 @@ class ToucanTTSInterface(torch.nn.Module):
         sweep over the words of a sentence in one call.
         ``loudness`` / ``peak_ceiling`` (as in ``synthesize_batch``): every variant is normalised on its own and its dict gains
         ``loudness``, its float64 [8] row of statistics on the device; ``self.last_loudness`` holds all rows, in variant order.
+        ``true_peak_ceiling`` / ``limiter`` (as in ``synthesize_batch``): every dict also gains ``delivery``, its float64 [8] row of
+        ``truepeak.DELIVERY_COLUMNS``, and ``self.last_delivery`` holds all rows, in variant order.
         ``speech_level`` (as in ``synthesize_batch``) likewise: every dict gains ``speech_activity`` = (its stats row [8], its runs
         [64, 2], its counts [16]) - what ``pause_duration_scaling_factor`` really did to the pauses can be read from the runs
         (``activity.pauses``) - and ``self.last_speech_activity`` holds all rows, in variant order.
@@ -596,7 +650,8 @@ class ToucanTTSInterface(torch.nn.Module):
             pronunciation.check_beam(beam)
         normalise = self._check_loudness(loudness, peak_ceiling)
         level = self._check_speech_level(loudness, speech_level, peak_ceiling)
-        rows, activity_rows = [], []
+        delivery = self._check_delivery(loudness, speech_level, true_peak_ceiling, limiter)
+        rows, activity_rows, delivery_rows = [], [], []
         variants = prosody.grid(duration_scaling_factors, pitch_variance_scales, energy_variance_scales, pause_duration_scaling_factors)
         which = [None] * len(variants)  # the curve alternative of every variant
         if curves is not None:
@@ -627,9 +682,11 @@ class ToucanTTSInterface(torch.nn.Module):
                 if check_pronunciation:
                     host24 = wav24.float().cpu().numpy()
                     checked = self._checker().check([phones.float().cpu().numpy()] * n, [host24[b:b + m] for b, m in spans24], self.SAMPLE_RATE, beam=beam)
-                wav24 = self._normalize(wav24, spans24, loudness, peak_ceiling, speech_level)
+                wav24 = self._normalize(wav24, spans24, loudness, peak_ceiling, speech_level, true_peak_ceiling, limiter)
                 if normalise:
                     rows.append(self.last_loudness)
+                if delivery:
+                    delivery_rows.append(self.last_delivery)
                 if level:
                     activity_rows.append(self.last_speech_activity)
                 wav, spans = self._convert(wav24, spans24, sample_rate, pcm16)
@@ -640,6 +697,8 @@ class ToucanTTSInterface(torch.nn.Module):
                         results[-1]["pronunciation"] = checked[i]
                     if normalise:
                         results[-1]["loudness"] = rows[-1][i]
+                    if delivery:
+                        results[-1]["delivery"] = delivery_rows[-1][i]
                     if level:
                         results[-1]["speech_activity"] = tuple(t[i] for t in activity_rows[-1])
                     if curves is not None:  # (a chunk whose alternatives are all None took the path without curves: no Spans, no blocks)
@@ -648,18 +707,23 @@ class ToucanTTSInterface(torch.nn.Module):
                         results[-1].update(curve=which[lo + i], span_stats=(none, none) if per is None else per[i])
             if normalise:
                 self.last_loudness = torch.cat(rows)
+            if delivery:
+                self.last_delivery = torch.cat(delivery_rows)
             if level:
                 self.last_speech_activity = tuple(torch.cat([r[k] for r in activity_rows]) for k in range(3))
         return results
 
     def stream(self, text, input_is_phones=False, chunk_frames=512, halo_frames=None, max_batch=4, z_noise=None, sample_rate=None, pcm16=False, loudness=None,
-               peak_ceiling=-1.0, speech_level=None, **prosody):
+               peak_ceiling=-1.0, speech_level=None, true_peak_ceiling=None, limiter=False, **prosody):
         """Generator of waveform pieces for ONE (long) text: the acoustic model runs once, the vocoder chunk-wise with overlap
         (streaming.py) - the concatenation equals ``self(text, ...)`` bit for bit, the first piece is ready after one chunk and the
         vocoder's workspace is bounded by ``max_batch`` chunks.  prosody: the keyword arguments of ``forward`` (gold durations /
         pitch / energy, scaling factors, ``prosody_curves``).  ``sample_rate`` / ``pcm16``: the pieces at another rate and / or as int16, converted as
         they come (resample.Resampler.streamer); their concatenation equals ``self(text, sample_rate=..., pcm16=...)`` bit for bit.
-        ``loudness`` and ``speech_level`` raise ValueError: both are properties of the whole utterance, which a stream does not have."""
+        ``loudness`` and ``speech_level`` raise ValueError: both are properties of the whole utterance, which a stream does not have;
+        so do ``true_peak_ceiling`` and ``limiter``, which belong to ``loudness``."""
+        if true_peak_ceiling is not None or limiter:
+            raise ValueError("stream() cannot hold a true-peak ceiling: the gain under it needs the whole utterance; use forward(loudness=..., true_peak_ceiling=...)")
         if loudness is not None:
             raise ValueError("stream() cannot normalise loudness: the integrated loudness needs the whole utterance; use forward(loudness=...)")
         if speech_level is not None:
@@ -714,7 +778,9 @@ class ToucanTTSInterface(torch.nn.Module):
                      pcm16=False,
                      loudness=None,
                      peak_ceiling=-1.0,
-                     speech_level=None):
+                     speech_level=None,
+                     true_peak_ceiling=None,
+                     limiter=False):
         """Same result as the reference's sentence loop (:231-285: silence, sentence, silence, ... with blank strings skipped,
         24 kHz float file or sample-doubled 48 kHz PCM16), but the sentences go through the engines as ragged batches of up to
         MAX_FILE_BATCH utterances and the file is assembled once on the host.  ``sample_rate`` / ``pcm16`` (additive): every
@@ -725,14 +791,19 @@ class ToucanTTSInterface(torch.nn.Module):
         reads a little below the sentences);
         ``self.last_loudness`` holds the rows of the spoken sentences in file order.  Not with ``increased_compatibility_mode``.
         ``speech_level`` (additive, as in ``synthesize_batch``) likewise: every sentence on its own, ``self.last_speech_activity``
-        holds the rows of the spoken sentences in file order; not with ``increased_compatibility_mode``."""
+        holds the rows of the spoken sentences in file order; not with ``increased_compatibility_mode``.
+        ``true_peak_ceiling`` / ``limiter`` (additive, as in ``synthesize_batch``): applied with ``loudness`` to every sentence on its
+        own; ``self.last_delivery`` holds the rows of the spoken sentences in file order; not with ``increased_compatibility_mode``."""
+        if increased_compatibility_mode and (true_peak_ceiling is not None or limiter):
+            raise ValueError("increased_compatibility_mode is the reference's path as it is: it does not combine with true_peak_ceiling / limiter")
         if increased_compatibility_mode and loudness is not None:
             raise ValueError("increased_compatibility_mode is the reference's path as it is: it does not combine with loudness")
         if increased_compatibility_mode and speech_level is not None:
             raise ValueError("increased_compatibility_mode is the reference's path as it is: it does not combine with speech_level")
         normalise = self._check_loudness(loudness, peak_ceiling)
         level = self._check_speech_level(loudness, speech_level, peak_ceiling)
-        activity_rows = {}
+        delivery = self._check_delivery(loudness, speech_level, true_peak_ceiling, limiter)
+        activity_rows, delivery_rows = {}, {}
         if increased_compatibility_mode and (sample_rate is not None or pcm16):
             raise ValueError("increased_compatibility_mode is the reference's sample doubling to 48 kHz PCM16: it does not combine with "
                              "sample_rate / pcm16")
@@ -759,15 +830,20 @@ class ToucanTTSInterface(torch.nn.Module):
                                               energy=[enes[i] for i in idx] if has_e else None,
                                               duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
                                               energy_variance_scale=energy_variance_scale, sample_rate=sample_rate, pcm16=pcm16,
-                                              loudness=loudness, peak_ceiling=peak_ceiling, speech_level=speech_level)
+                                              loudness=loudness, peak_ceiling=peak_ceiling, speech_level=speech_level,
+                                              true_peak_ceiling=true_peak_ceiling, limiter=limiter)
                 for r, (i, w) in enumerate(zip(idx, waves)):
                     pieces[i] = w.cpu().numpy()
                     if normalise:
                         rows[i] = self.last_loudness[r]
+                    if delivery:
+                        delivery_rows[i] = self.last_delivery[r]
                     if level:
                         activity_rows[i] = tuple(t[r] for t in self.last_speech_activity)
         if normalise:
             self.last_loudness = torch.stack([rows[i] for i in spoken]) if spoken else torch.zeros((0, 8), dtype=torch.float64, device=self.device)
+        if delivery:
+            self.last_delivery = torch.stack([delivery_rows[i] for i in spoken]) if spoken else torch.zeros((0, 8), dtype=torch.float64, device=self.device)
         if level:
             empty = (torch.zeros((0, 8), dtype=torch.float64, device=self.device), torch.zeros((0, 64, 2), dtype=torch.int64, device=self.device),
                      torch.zeros((0, 16), dtype=torch.int64, device=self.device))

@@ -1,7 +1,8 @@
 """Integrated loudness after ITU-R BS.1770-4 and loudness normalisation on the GPU (csrc/loudness.hip, include/toucan_loudness.h)
 for a ragged batch of waveforms: K-weighting, 400 ms blocks with 75 % overlap, the absolute gate at -70 LUFS and the relative gate
 10 LU below the mean of what the absolute gate keeps; then one gain per utterance that brings it to a target, limited by a
-SAMPLE-peak ceiling (max |x|; not a 4x oversampled true peak).  include/toucan_loudness.h holds the definition, DESIGN.md section
+SAMPLE-peak ceiling (max |x|; not a 4x oversampled true peak: truepeak.py has that one, as ``true_peak_ceiling=`` /
+``limiter=`` beside ``loudness=``).  include/toucan_loudness.h holds the definition, DESIGN.md section
 17 the decisions, tests/loudness_ref.py the float64 restatement.
 
 The coefficients are the bilinear transforms of the analogue prototypes, in float64 on the host once per rate; at 48 kHz they are

@@ -30,7 +30,8 @@
  * -0.691 + 10 log10 (mean of the z_j both gates keep), and -inf for an utterance shorter than four segments or without a block
  * past the absolute gate.  Every sum runs in index order in fp64.
  *
- * Normalisation to the target L_t (LUFS) under the ceiling c (dBFS, a SAMPLE peak: max |x|, not a 4x oversampled true peak):
+ * Normalisation to the target L_t (LUFS) under the ceiling c (dBFS, a SAMPLE peak: max |x|, not a 4x oversampled true peak - that
+ * one, the gain under it and a limiter are toucan_truepeak.h's, the interface's true_peak_ceiling= / limiter=):
  *     g = min(10^((L_t - L) / 20), 10^(c / 20) / peak),    g = 1 where L = -inf or peak = 0,
  * rounded to float32 once (towards zero as far as needed for float32(peak g) <= 10^(c / 20) where the ceiling is what limits
  * it); y = x g is one fp32 multiply per sample.
