@@ -320,6 +320,17 @@ TRUEPEAK_PROTOTYPES = {
 # include/toucan_truepeak.h TTS_TRUEPEAK_TAPS, _HALF_WIDTH, _MAX_STEPS, _TILED_ROUNDS, _SHORT_TERM_SEGMENTS, TTS_DELIVERY_COLUMNS, TTS_LIMITER_COLUMNS
 TRUEPEAK_TAPS, TRUEPEAK_HALF_WIDTH, TRUEPEAK_MAX_STEPS, TRUEPEAK_TILED_ROUNDS, TRUEPEAK_SHORT_TERM_SEGMENTS, DELIVERY_N_COLUMNS, LIMITER_N_COLUMNS = 15, 7, 128, 3, 30, 12, 8
 
+# symbol -> (restype, argtypes); mirrors include/toucan_fidelity.h (reflection framing, spectral distances of a pair of waveforms: csrc/fidelity.hip) one to one
+FIDELITY_PROTOTYPES = {
+    "tts_spectral_frames_per_group": (C.c_int, []),
+    "tts_spectral_reduce_sweep": (C.c_int, []),
+    "tts_frame_reflect": (C.c_int, [_p, _l, _p, _p, _i, _l, _i, _p, _p, _l, _p, _p]),
+    "tts_spectral_distance": (C.c_int, [_p, _l, _i, _l, _p, _p, _i, _l, _p, _p, _i, _p, _i, _p, _p]),
+    "tts_spectral_reduce": (C.c_int, [_p, _p, _i, _l, _p, _p]),
+}
+# include/toucan_fidelity.h TTS_FIDELITY_SUMS, _MAX_BINS, _MAX_BANDS, _MAX_HOP
+FIDELITY_SUMS, FIDELITY_MAX_BINS, FIDELITY_MAX_BANDS, FIDELITY_MAX_HOP = 4, 2049, 256, 4096
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -346,7 +357,7 @@ def lib():
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
             list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()) + \
             list(PRONUNCIATION_PROTOTYPES.items()) + list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()) + \
-            list(TRUEPEAK_PROTOTYPES.items()):
+            list(TRUEPEAK_PROTOTYPES.items()) + list(FIDELITY_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

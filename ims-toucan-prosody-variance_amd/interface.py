@@ -546,6 +546,38 @@ class ToucanTTSInterface(torch.nn.Module):
                 r.update(synth=s, recording=w, recording_sr=sr)
         return results
 
+    def vocoder_fidelity(self, recordings, sr=None, keep_waves=False):
+        """Additive API: copy-synthesis of ``recordings`` through this interface's own vocoder, at the precision it runs at
+        (fidelity.CopySynthesis): every recording goes to 24 kHz and is cut to whole mel frames, its 16 kHz /
+        80-bin log-mel - what the acoustic model would hand the vocoder - is vocoded, and the result is compared with the cut
+        recording: ``mel_l1`` (the reference's vocoder training loss without its weight), the frame it is worst at, and per STFT
+        resolution the spectral convergence and the log-magnitude L1.  recordings: paths (style.read_audio), (wave, sample rate)
+        tuples, or waveforms at ``sr``; several channels are averaged.  -> one dict per recording
+        (``fidelity.SpectralDistance.distance`` documents it); with ``keep_waves`` it also holds "generated" and "recording", the
+        two 24 kHz signals that were compared, on the device.  Everything from the first resampling on stays on the device."""
+        from . import fidelity, style
+        if getattr(self, "_fidelity_obj", None) is None:
+            vocode = self.mel2wav.vocode if self.pipe is not None else self.mel2wav.forward
+            self._fidelity_obj = fidelity.CopySynthesis(vocode, self.device)
+        waves, rates = [], []
+        for r in recordings:
+            if isinstance(r, (str, os.PathLike)):
+                data, rate = style.read_audio(r)
+            elif isinstance(r, tuple):
+                data, rate = r
+            else:
+                if sr is None:
+                    raise ValueError("waveforms need their sample rate: vocoder_fidelity(waves, sr=...)")
+                data, rate = r, sr
+            waves.append(data)
+            rates.append(int(rate))
+        results = [None] * len(waves)
+        for rate in sorted(set(rates)):  # one batch holds one rate
+            idx = [i for i, x in enumerate(rates) if x == rate]
+            for i, rec in zip(idx, self._fidelity_obj.run([waves[i] for i in idx], rate, keep_waves=keep_waves)):
+                results[i] = rec
+        return results
+
     def _checker(self):
         """The pronunciation checker, built on first use from the aligner checkpoint the cloner loads (Models/Aligner/aligner.pt)."""
         if getattr(self, "_checker_obj", None) is None:
