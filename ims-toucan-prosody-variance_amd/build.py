@@ -17,7 +17,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(PKG, "..", "include", h) for h in ("toucan_tts.h", "toucan_align.h", "toucan_score.h", "toucan_gan.h", "toucan_pitch.h", "toucan_train.h", "toucan_resample.h", "toucan_prosody.h", "toucan_prosody_curves.h", "toucan_compare.h", "toucan_pronunciation.h", "toucan_loudness.h", "toucan_truepeak.h", "toucan_activity.h", "toucan_fidelity.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(PKG, "..", "include", h) for h in ("toucan_tts.h", "toucan_align.h", "toucan_score.h", "toucan_gan.h", "toucan_pitch.h", "toucan_train.h", "toucan_resample.h", "toucan_prosody.h", "toucan_prosody_curves.h", "toucan_prosody_fit.h", "toucan_compare.h", "toucan_pronunciation.h", "toucan_loudness.h", "toucan_truepeak.h", "toucan_activity.h", "toucan_fidelity.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

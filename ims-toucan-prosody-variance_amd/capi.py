@@ -257,6 +257,15 @@ CURVE_PROTOTYPES = {
 }
 PROSODY_CURVE_COLUMNS = 5  # include/toucan_prosody_curves.h TTS_PROSODY_CURVE_COLUMNS
 
+# symbol -> (restype, argtypes); mirrors include/toucan_prosody_fit.h (the time budget: csrc/prosody.hip, stage entries in csrc/pipeline.hip)
+FIT_PROTOTYPES = {
+    "tts_prosody_fit": (C.c_int, [_p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "tts_prosody_fit_apply": (C.c_int, [_p, _p, _i, _p]),
+    "tts_control_and_regulate_t": (C.c_int, [_p, _p, _p, _p, _i, _p, _i, _p, _p]),
+    "tts_copy_prosody_fit": (C.c_int, [_p, _p, _p, _p, _p]),
+}
+FIT_UTT_DURATION, FIT_UTT_PAUSE, FIT_SPAN = 0, 1, 2  # include/toucan_prosody_fit.h TTS_FIT_UTT_DURATION, _UTT_PAUSE, _SPAN
+FIT_SPEC, FIT_N_COLUMNS, FIT_MAX_TARGET, FIT_MAX_BOUND = 4, 8, 1 << 24, 64  # TTS_FIT_SPEC, TTS_FIT_COLUMNS, TTS_FIT_MAX_TARGET, TTS_FIT_MAX_BOUND
 
 
 class TtsDtwPair(C.Structure):
@@ -357,7 +366,7 @@ def lib():
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
             list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()) + \
             list(PRONUNCIATION_PROTOTYPES.items()) + list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()) + \
-            list(TRUEPEAK_PROTOTYPES.items()) + list(FIDELITY_PROTOTYPES.items()):
+            list(TRUEPEAK_PROTOTYPES.items()) + list(FIDELITY_PROTOTYPES.items()) + list(FIT_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -8,6 +8,7 @@
 //   tts_control_and_regulate  InferenceToucanTTS.py:214-235 (+ _scale_variance :333-343, LengthRegulator.py:37-61)
 //   tts_control_and_regulate_v  the same with per-utterance scales and the statistics around them (include/toucan_prosody.h)
 //   tts_control_and_regulate_c  the same with a per-phoneme curve table and span statistics (include/toucan_prosody_curves.h)
+//   tts_control_and_regulate_t  the same with utterances, pauses or spans fitted to a number of frames (include/toucan_prosody_fit.h)
 //   tts_teacher_forced        the scorer's replacement of the two above: ToucanTTS.py:321-330 (include/toucan_score.h)
 //   tts_decoder               decoder Conformer + feat_out (InferenceToucanTTS.py:238-239)
 //   tts_postnet               PostNet.forward + residual (PostNet.py:62-74, InferenceToucanTTS.py:241)
@@ -28,6 +29,7 @@
 #include "common.h"
 #include "../../include/toucan_prosody.h"
 #include "../../include/toucan_prosody_curves.h"
+#include "../../include/toucan_prosody_fit.h"
 #include "../../include/toucan_score.h"
 
 namespace tts {
@@ -209,6 +211,10 @@ struct Handle {
   std::vector<float> pstats_host;    // the utterance blocks, read back with the durations; empty if the batch went through the scalar entry
   int n_spans = -1;                  // spans of the last tts_control_and_regulate_c of the batch in flight; -1: it did not run
   std::vector<float> sstats_host;    // [2][n_spans][TTS_PROSODY_STATS], read back with the durations
+  float* fit_ws = nullptr;           // in the phoneme arena: scales_out [B][4] | curves_out [R][5] | report [R][8] | extra [R] (tts_control_and_regulate_t)
+  int n_fit = -1;                    // segments of the last tts_control_and_regulate_t of the batch in flight; -1: it did not run
+  std::vector<float> fit_host;       // its report [n_fit][TTS_FIT_COLUMNS], then the solved scales [B][TTS_PROSODY_SCALES]: read back likewise
+  std::vector<int> fit_extra_host;   // and its extra frames [R]
   bool have_flow = false;
   // profiling (bench.py's roofline leg): event pairs around the launches of the selected kernel class ("" = every class)
   bool prof_on = false, prof_detail = false;
@@ -857,7 +863,9 @@ size_t conformer_bytes(size_t R) { return R * (ATT * 4 * 4 + 1536 * 4 + 3 * ATT 
 size_t phone_arena_bytes(size_t R, size_t B) {
   return conformer_bytes(R) + R * (100 + 3 * ATT + 6 * 256 + 16) * 4 + B * (64 + 2 * ATT + 24 * 256 + 8) * 4 + (1 << 16) +
          2 * (B + R) * TTS_PROSODY_STATS * 4 + 256 +  // (the statistics blocks of tts_control_and_regulate_v and _c: utterances, at most R spans)
-         2 * B * TTS_PROSODY_STATS * 4 + 256;  // (once a second statistics buffer; kept, so that tts_workspace_bytes answers as it did)
+         2 * B * TTS_PROSODY_STATS * 4 + 256 +  // (once a second statistics buffer; kept, so that tts_workspace_bytes answers as it did)
+         // tts_control_and_regulate_t: the written scales and curves, the extra frames, the report of at most R segments
+         B * TTS_PROSODY_SCALES * 4 + R * (TTS_PROSODY_CURVE_COLUMNS + 1 + TTS_FIT_COLUMNS) * 4 + 4 * 256;
 }
 // cond_buffer: the PostFlow keeps the coupling blocks' conditioning [RS, 1536] in memory (every configuration but the 16-bit ones
 // with the fused WaveNet layer, which computes it inside the layer).  Those configurations run a coupling block as one launch: the
@@ -1017,6 +1025,10 @@ int pipeline_encoder(Handle* h, const float* text, const float* utt_emb, const i
   h->pstats_host.clear();
   h->n_spans = -1;
   h->sstats_host.clear();
+  h->fit_ws = nullptr;
+  h->n_fit = -1;
+  h->fit_host.clear();
+  h->fit_extra_host.clear();
   const int R = h->lp.total;
   TTS_TRY(arena_reserve(h->phone, phone_arena_bytes(R, B), st));
   TTS_TRY(ensure_ptabs(h, st));
@@ -1148,13 +1160,56 @@ int regulate(Handle* h, const int* dur_dev, bool gold, int* frames_out, hipStrea
 // What one of the three entries asks for (include/toucan_tts.h, toucan_prosody.h, toucan_prosody_curves.h).
 struct ControlRequest {
   const char* entry;                      // its name, for messages
-  enum { BATCH, UTTERANCE, PHONEME } kind;  // the scalar, the _v, the _c entry; the last two take the statistics
+  enum { BATCH, UTTERANCE, PHONEME, FIT } kind;  // the scalar, the _v, the _c, the _t entry; the last three take the statistics
   float batch[4] = {1.f, 1.f, 1.f, 1.f};  // the scalar entry's scales: duration, pitch variance, energy variance, pause
-  const float* scales = nullptr;          // host [B][4]: UTTERANCE, and optional with PHONEME
-  const float* curves = nullptr;          // host [R][5]: PHONEME only
+  const float* scales = nullptr;          // host [B][4]: UTTERANCE, and optional with PHONEME and FIT
+  const float* curves = nullptr;          // host [R][5]: PHONEME, and optional with FIT
   const int* spans = nullptr;             // host [n_spans][2] packed row ranges, with curves only
   int n_spans = 0;
+  const float* segments = nullptr;        // host [n_seg][TTS_FIT_COLUMNS]: FIT only (include/toucan_prosody_fit.h)
+  int n_seg = 0;
 };
+
+// The _t entry's segment table against the batch's layout: everything include/toucan_prosody_fit.h asks of it.
+int check_fit_segments(const char* entry, const Layout& lp, const float* seg, int n_seg) {
+  const int B = lp.n(), R = lp.total;
+  TTS_CHECK_ARG(seg && n_seg >= 1, "%s: %d segments and %s segment table (a call without segments takes tts_control_and_regulate_c)", entry, n_seg,
+                seg ? "a" : "no");
+  TTS_CHECK_ARG(n_seg <= R, "%s: %d segments, the batch has %d phoneme rows", entry, n_seg, R);
+  TTS_CHECK_ARG(R <= TTS_FIT_MAX_TARGET, "%s: %d phoneme rows, the segment table holds row numbers up to 2^24", entry, R);
+  std::vector<int> whole(B, 0), parts(B, 0);
+  std::vector<std::pair<int, int>> order;  // (begin, segment)
+  for (int s = 0; s < n_seg; ++s) {
+    const float* q = seg + (size_t)s * TTS_FIT_COLUMNS;
+    for (int k = 0; k < TTS_FIT_COLUMNS; ++k) TTS_CHECK_ARG(std::isfinite(q[k]), "%s: segment %d: column %d is %g, it must be finite", entry, s, k, (double)q[k]);
+    TTS_CHECK_ARG(q[0] >= 0.f && q[0] < (float)B && q[0] == std::floor(q[0]), "%s: segment %d: utterance %g, the batch has %d", entry, s, (double)q[0], B);
+    const int u = (int)q[0];
+    TTS_CHECK_ARG(q[1] == (float)TTS_FIT_UTT_DURATION || q[1] == (float)TTS_FIT_UTT_PAUSE || q[1] == (float)TTS_FIT_SPAN,
+                  "%s: utterance %d, segment %d: kind %g is none of 0, 1, 2", entry, u, s, (double)q[1]);
+    const int kind = (int)q[1], b0 = lp.begins[u], b1 = b0 + lp.lengths[u];
+    TTS_CHECK_ARG(q[2] == std::floor(q[2]) && q[3] == std::floor(q[3]) && q[2] >= (float)b0 && q[2] < q[3] && q[3] <= (float)b1,
+                  "%s: utterance %d, segment %d: rows [%g, %g) are empty or outside the utterance's rows [%d, %d)", entry, u, s, (double)q[2],
+                  (double)q[3], b0, b1);
+    TTS_CHECK_ARG(kind == TTS_FIT_SPAN || ((int)q[2] == b0 && (int)q[3] == b1), "%s: utterance %d, segment %d: kind %d takes the whole utterance", entry,
+                  u, s, kind);
+    TTS_CHECK_ARG(q[4] >= 1.f && q[4] <= (float)TTS_FIT_MAX_TARGET && q[4] == std::floor(q[4]),
+                  "%s: utterance %d, segment %d: the target %g is no whole number of frames in 1 .. 2^24", entry, u, s, (double)q[4]);
+    TTS_CHECK_ARG(q[5] <= q[6] && q[6] <= (float)TTS_FIT_MAX_BOUND && (kind == TTS_FIT_UTT_PAUSE ? q[5] >= 0.f : q[5] > 0.f),
+                  "%s: utterance %d, segment %d: bounds [%g, %g] must be ordered, %s and at most %d", entry, u, s, (double)q[5], (double)q[6],
+                  kind == TTS_FIT_UTT_PAUSE ? "not negative" : "positive", TTS_FIT_MAX_BOUND);
+    TTS_CHECK_ARG(q[7] == 0.f || q[7] == 1.f, "%s: utterance %d, segment %d: exact is %g, not 0 or 1", entry, u, s, (double)q[7]);
+    (kind == TTS_FIT_SPAN ? parts : whole)[u] += 1;
+    TTS_CHECK_ARG(whole[u] <= 1 && !(whole[u] && parts[u]), "%s: utterance %d, segment %d: a whole-utterance segment stands alone in its utterance", entry,
+                  u, s);
+    order.emplace_back((int)q[2], s);
+  }
+  std::sort(order.begin(), order.end());
+  for (size_t i = 1; i < order.size(); ++i) {
+    const float* p = seg + (size_t)order[i - 1].second * TTS_FIT_COLUMNS;
+    TTS_CHECK_ARG((int)p[3] <= order[i].first, "%s: utterance %d: segments %d and %d overlap", entry, (int)p[0], order[i - 1].second, order[i].second);
+  }
+  return TTS_OK;
+}
 
 // A host array goes up through the table store of the acoustic stages under the key name + bytes (pinned staging, one asynchronous
 // copy on st).  The store already orders the reuse of its staging behind the last use of a generation, and a table that repeats -
@@ -1173,7 +1228,9 @@ int table_named(Handle* h, const char* name, const T* host, size_t n, hipStream_
 
 // Scalar entry: one control launch, then regulate().  Per-utterance entries: overrides -> statistics (utterances, spans) -> scales
 // and curves -> statistics (utterances, spans), then regulate(): its duration read-back is the one host round trip, and the
-// statistics ride on it (their copies are enqueued in front of it).  Nothing is enqueued before every value has been checked.
+// statistics ride on it (their copies are enqueued in front of it).  With segments the solver runs between the first statistics and
+// the control launch, which then reads the tables the solver wrote, and the repair's extra frames are added behind it; the report,
+// the solved scales and the extra frames ride on the same round trip.  Nothing is enqueued before every value has been checked.
 int control_regulate(Handle* h, const ControlRequest& q, int* frames_out, hipStream_t st) {
   TTS_CHECK_ARG(h && h->enc && h->dur, "%s: run tts_encoder and tts_variance_predictors first", q.entry);
   const int B = h->B, R = h->lp.total, n_spans = q.n_spans;
@@ -1183,6 +1240,15 @@ int control_regulate(Handle* h, const ControlRequest& q, int* frames_out, hipStr
     TTS_CHECK_ARG(q.curves, "%s: null curves", q.entry);
     TTS_CHECK_ARG(n_spans >= 0 && (q.spans || n_spans == 0), "%s: %d spans and %s span table", q.entry, n_spans, q.spans ? "a" : "no");
     TTS_CHECK_ARG(n_spans <= R, "%s: %d spans, the entry takes at most one per phoneme row (%d)", q.entry, n_spans, R);
+  }
+  const bool fit = q.kind == ControlRequest::FIT;
+  bool fit_spans = false;
+  if (fit) {
+    TTS_CHECK_ARG(n_spans >= 0 && (q.spans || n_spans == 0) && (q.curves || n_spans == 0), "%s: %d spans need a span table and a curve table", q.entry,
+                  n_spans);
+    TTS_CHECK_ARG(n_spans <= R, "%s: %d spans, the entry takes at most one per phoneme row (%d)", q.entry, n_spans, R);
+    TTS_TRY(check_fit_segments(q.entry, h->lp, q.segments, q.n_seg));
+    for (int s = 0; s < q.n_seg; ++s) fit_spans |= q.segments[(size_t)s * TTS_FIT_COLUMNS + 1] == (float)TTS_FIT_SPAN;
   }
   for (int u = 0; u < B; ++u) {
     if (q.scales) {
@@ -1227,11 +1293,48 @@ int control_regulate(Handle* h, const ControlRequest& q, int* frames_out, hipStr
     h->pstats = ps;
   }
   float *ubefore = h->pstats, *uafter = ubefore + NU, *xbefore = uafter + NU, *xafter = xbefore + NX;
+  const int n_seg = q.n_seg;
+  const int *gb = nullptr, *ge = nullptr, *gu = nullptr, *gk = nullptr;
+  const float* gspec = nullptr;
+  float *fit_scales = nullptr, *fit_curves = nullptr, *fit_report = nullptr;
+  int* fit_extra = nullptr;
+  if (fit) {  // the segment table as the kernel takes it: (begin | end | utterance | kind)[n_seg] and [n_seg][target, lo, hi, exact]
+    std::vector<int> ints(4 * (size_t)n_seg);
+    std::vector<float> spec((size_t)n_seg * TTS_FIT_SPEC);
+    for (int s = 0; s < n_seg; ++s) {
+      const float* g = q.segments + (size_t)s * TTS_FIT_COLUMNS;
+      ints[s] = (int)g[2];
+      ints[n_seg + s] = (int)g[3];
+      ints[2 * (size_t)n_seg + s] = (int)g[0];
+      ints[3 * (size_t)n_seg + s] = (int)g[1];
+      for (int k = 0; k < TTS_FIT_SPEC; ++k) spec[(size_t)s * TTS_FIT_SPEC + k] = g[4 + k];
+    }
+    TTS_TRY(table_named(h, "prosody_fit_rows", ints.data(), ints.size(), st, &gb));
+    TTS_TRY(table_named(h, "prosody_fit_spec", spec.data(), spec.size(), st, &gspec));
+    ge = gb + n_seg; gu = ge + n_seg; gk = gu + n_seg;
+    if (!h->fit_ws) {
+      TTS_ALLOC(ws, h->phone, float, (size_t)B * TTS_PROSODY_SCALES + (size_t)R * (TTS_PROSODY_CURVE_COLUMNS + TTS_FIT_COLUMNS + 1));
+      h->fit_ws = ws;
+    }
+    fit_scales = h->fit_ws;
+    fit_curves = fit_scales + (size_t)B * TTS_PROSODY_SCALES;
+    fit_report = fit_curves + (size_t)R * TTS_PROSODY_CURVE_COLUMNS;
+    fit_extra = reinterpret_cast<int*>(fit_report + (size_t)R * TTS_FIT_COLUMNS);
+    if (!q.curves && !fit_spans) fit_curves = nullptr;
+  }
   TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, nullptr, st));
   TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, ubefore, st));
   TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, xb, xe, n_spans, xbefore, st));  // (no spans: no launch)
-  if (q.curves) TTS_TRY(tts_prosody_control_c(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, sdev, cdev, st));
-  else TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, sdev, st));
+  if (fit) {  // the solver writes tables of its own in the workspace: those of the table store are shared between batches
+    TTS_TRY(tts_prosody_fit(h->text, 62, h->dur, pb, pe, B, gb, ge, gu, gk, n_seg, gspec, sdev, cdev, fit_scales, fit_curves, fit_extra, fit_report, st));
+    if (fit_curves) TTS_TRY(tts_prosody_control_c(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, fit_scales, fit_curves, st));
+    else TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, fit_scales, st));
+    TTS_TRY(tts_prosody_fit_apply(h->dur, fit_extra, R, st));
+  } else if (q.curves) {
+    TTS_TRY(tts_prosody_control_c(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, sdev, cdev, st));
+  } else {
+    TTS_TRY(tts_prosody_control_v(h->text, 62, h->pitch, h->energy, h->dur, pb, pe, B, sdev, st));
+  }
   TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, pb, pe, B, uafter, st));
   TTS_TRY(tts_prosody_stats(h->pitch, h->energy, h->dur, xb, xe, n_spans, xafter, st));
   h->pstats_host.assign(2 * NU, 0.f);
@@ -1239,8 +1342,23 @@ int control_regulate(Handle* h, const ControlRequest& q, int* frames_out, hipStr
   if (q.curves) h->sstats_host.assign(2 * NX, 0.f);
   if (n_spans > 0)
     TTS_TRY(hip_ok(hipMemcpyAsync(h->sstats_host.data(), xbefore, 2 * NX * sizeof(float), hipMemcpyDeviceToHost, st), "span statistics to host"));
+  if (fit) {
+    const size_t NR = (size_t)n_seg * TTS_FIT_COLUMNS, NS = (size_t)B * TTS_PROSODY_SCALES;
+    h->fit_host.assign(NR + NS, 0.f);
+    h->fit_extra_host.assign(R, 0);
+    TTS_TRY(hip_ok(hipMemcpyAsync(h->fit_host.data(), fit_report, NR * sizeof(float), hipMemcpyDeviceToHost, st), "fit report to host"));
+    TTS_TRY(hip_ok(hipMemcpyAsync(h->fit_host.data() + NR, fit_scales, NS * sizeof(float), hipMemcpyDeviceToHost, st), "fitted scales to host"));
+    TTS_TRY(hip_ok(hipMemcpyAsync(h->fit_extra_host.data(), fit_extra, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, st), "extra frames to host"));
+  }
   const int rc = regulate(h, h->dur, false, frames_out, st);  // (synchronises st once: durations and statistics are on the host)
   if (rc != TTS_OK) h->pstats_host.clear();
+  if (fit) {
+    h->n_fit = rc == TTS_OK ? n_seg : -1;
+    if (rc != TTS_OK) {
+      h->fit_host.clear();
+      h->fit_extra_host.clear();
+    }
+  }
   if (q.curves) {
     h->n_spans = rc == TTS_OK ? n_spans : -1;
     if (rc != TTS_OK) h->sstats_host.clear();
@@ -1744,6 +1862,30 @@ int tts_control_and_regulate_c(TtsHandle* h, const float* scales, const float* c
   q.spans = spans;
   q.n_spans = n_spans;
   return tts::stage_done(H(h), 0, ST(stream), tts::control_regulate(H(h), q, frame_counts, ST(stream)));
+}
+int tts_control_and_regulate_t(TtsHandle* h, const float* scales, const float* curves, const int32_t* spans, int32_t n_spans,
+                               const float* segments, int32_t n_seg, int32_t* frame_counts, tts_stream_t stream) {
+  tts::ControlRequest q{"tts_control_and_regulate_t", tts::ControlRequest::FIT};
+  q.scales = scales;
+  q.curves = curves;
+  q.spans = spans;
+  q.n_spans = n_spans;
+  q.segments = segments;
+  q.n_seg = n_seg;
+  return tts::stage_done(H(h), 0, ST(stream), tts::control_regulate(H(h), q, frame_counts, ST(stream)));
+}
+int tts_copy_prosody_fit(TtsHandle* h, float* report, float* scales, int32_t* extra, tts_stream_t stream) {
+  (void)stream;  // (everything came back with the durations: a host copy)
+  tts::Handle* hh = H(h);
+  if (!hh || hh->n_fit < 0) {
+    tts::set_error("tts_copy_prosody_fit: the batch in flight did not go through tts_control_and_regulate_t");
+    return TTS_E_ARG;
+  }
+  const size_t nr = (size_t)hh->n_fit * TTS_FIT_COLUMNS, ns = (size_t)hh->B * TTS_PROSODY_SCALES;
+  if (report) memcpy(report, hh->fit_host.data(), nr * sizeof(float));
+  if (scales) memcpy(scales, hh->fit_host.data() + nr, ns * sizeof(float));
+  if (extra && !hh->fit_extra_host.empty()) memcpy(extra, hh->fit_extra_host.data(), hh->fit_extra_host.size() * sizeof(int32_t));
+  return TTS_OK;
 }
 int tts_copy_prosody_span_stats(TtsHandle* h, float* before, float* after, tts_stream_t stream) {
   (void)stream;  // (the blocks came back with the durations: a host copy)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import capi, packing, prosody
+from . import prosody_fit as prosody_fit_mod
 from .capi import (ACT_NONE, ACT_RELU, ACT_TANH, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32, COMPUTE_F32X3, MODE_COUPLING, MODE_GATED, MODE_GLU,
                    MODE_LINEAR, PRE_LRELU, PRE_NONE, PRE_SNAKE)
 from .ragged import Ragged
@@ -318,6 +319,24 @@ class Ops:
         capi.check(self.lib.tts_prosody_control_c(text.data_ptr(), _ld(text), pitch.data_ptr(), energy.data_ptr(), dur.data_ptr(),
                                                   sb.data_ptr(), se.data_ptr(), rag.n_seq, _ptr(scales), curves.data_ptr(), self.stream()),
                    "tts_prosody_control_c")
+
+    def prosody_fit(self, text, dur, rag, seg_rows, seg_spec, scales, curves, scales_out, curves_out, extra, report):
+        """tts_prosody_fit (include/toucan_prosody_fit.h): ``seg_rows`` int32 [4, n_seg] (begin | end | utterance | kind) and
+        ``seg_spec`` float32 [n_seg, 4] (target, lo, hi, exact) on the device; scales / curves: the input tables or None; the four
+        outputs are written (curves_out may be None without curves and spans)."""
+        sb, se = rag.bounds()
+        n = int(seg_rows.shape[1])
+        assert seg_rows.dtype == torch.int32 and seg_rows.is_contiguous() and seg_rows.shape[0] == 4 and tuple(seg_spec.shape) == (n, capi.FIT_SPEC)
+        assert tuple(scales_out.shape) == (rag.n_seq, capi.PROSODY_SCALES) and tuple(report.shape) == (n, capi.FIT_N_COLUMNS)
+        assert extra.dtype == torch.int32 and extra.numel() == rag.total_rows
+        assert curves_out is None or tuple(curves_out.shape) == (rag.total_rows, capi.PROSODY_CURVE_COLUMNS)
+        capi.check(self.lib.tts_prosody_fit(text.data_ptr(), _ld(text), dur.data_ptr(), sb.data_ptr(), se.data_ptr(), rag.n_seq,
+                                            seg_rows[0].data_ptr(), seg_rows[1].data_ptr(), seg_rows[2].data_ptr(), seg_rows[3].data_ptr(), n,
+                                            seg_spec.data_ptr(), _ptr(scales), _ptr(curves), scales_out.data_ptr(), _ptr(curves_out),
+                                            extra.data_ptr(), report.data_ptr(), self.stream()), "tts_prosody_fit")
+
+    def prosody_fit_apply(self, dur, extra):
+        capi.check(self.lib.tts_prosody_fit_apply(dur.data_ptr(), extra.data_ptr(), dur.numel(), self.stream()), "tts_prosody_fit_apply")
 
     def prosody_span_stats(self, pitch, energy, dur, ranges, stats):
         """tts_prosody_stats over arbitrary packed row ranges: ``ranges`` = (begin[n] | end[n]) as an int32 [2, n] device tensor."""
@@ -624,10 +643,12 @@ class AcousticEngine:
         return out.view(-1)
 
     # ---- stage A: everything up to the final per-phoneme durations (no data-dependent shapes) ----------------
-    def _stage_a(self, text, emb, lang_idx, gold_p, gold_e, gold_d, rag_p, rag_b, scales, taps=None, curves=None, ranges=None):
+    def _stage_a(self, text, emb, lang_idx, gold_p, gold_e, gold_d, rag_p, rag_b, scales, taps=None, curves=None, ranges=None, seg_rows=None,
+                 seg_spec=None, fit_spans=False):
         """Conformer.py:92-134, VariancePredictor / DurationPredictor, InferenceToucanTTS.py:214-227.  curves ([R, 5] device table,
         then ``scales`` is a [B, 4] tensor or None) and ranges ((begin | end) [2, n] of the spans, or None): the launches of
-        tts_control_and_regulate_c in its order."""
+        tts_control_and_regulate_c in its order.  seg_rows / seg_spec (Ops.prosody_fit's tables; fit_spans: a segment is a span):
+        the launches of tts_control_and_regulate_t in its order, scales and curves optional."""
         ops = self.ops
         ops.split_k = 2  # phoneme stages (fp32 configuration): the split forms at every grid size - see Ops.__init__
         R, B = text.shape[0], emb.shape[0]
@@ -669,7 +690,7 @@ class AcousticEngine:
             d.copy_(gold_d)
         if taps is not None:
             taps.update(enc_out=enc.clone(), pitch_raw=p.clone(), energy_raw=en.clone())
-        if curves is None and not torch.is_tensor(scales):  # one set of scalars for the batch: no statistics
+        if curves is None and seg_rows is None and not torch.is_tensor(scales):  # one set of scalars for the batch: no statistics
             ops.prosody_control(text, p, en, d, rag_p, *scales)
             return enc, p, en, d
         # per-utterance scales [B, 4] and / or per-phoneme curves: overrides -> statistics (utterances, spans) -> scales and curves ->
@@ -685,6 +706,18 @@ class AcousticEngine:
 
         ops.prosody_control_v(text, p, en, d, rag_p, None)
         measure(0)
+        if seg_rows is not None:  # the solver writes tables of its own; the control kernel reads those; the repair's frames follow it
+            scales_out = ops.empty(B, capi.PROSODY_SCALES)
+            curves_out = ops.empty(R, capi.PROSODY_CURVE_COLUMNS) if curves is not None or fit_spans else None
+            extra, report = ops.empty(R, dtype=torch.int32), ops.empty(int(seg_rows.shape[1]), capi.FIT_N_COLUMNS)
+            ops.prosody_fit(text, d, rag_p, seg_rows, seg_spec, scales, curves, scales_out, curves_out, extra, report)
+            if curves_out is None:
+                ops.prosody_control_v(text, p, en, d, rag_p, scales_out)
+            else:
+                ops.prosody_control_c(text, p, en, d, rag_p, scales_out, curves_out)
+            ops.prosody_fit_apply(d, extra)
+            measure(1)
+            return enc, p, en, d, stats, (None if curves is None else span_stats[:, :n]), report, scales_out, extra
         if curves is None:
             ops.prosody_control_v(text, p, en, d, rag_p, scales)
         else:
@@ -724,7 +757,7 @@ class AcousticEngine:
     @torch.inference_mode()
     def forward(self, texts, utt_embs, lang_ids=None, durations=None, pitch=None, energy=None, z_noise=None,
                 duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
-                pause_duration_scaling_factor=1.0, run_postflow=True, taps=None, generator=None, prosody_curves=None):
+                pause_duration_scaling_factor=1.0, run_postflow=True, taps=None, generator=None, prosody_curves=None, prosody_fit=None):
         """texts: list of [L_u,62] float tensors; utt_embs: [B,64]; lang_ids: list of int or None;
         durations/pitch/energy: optional lists (gold values, InferenceToucanTTS.py:209-211);
         the four scales: a scalar for the batch, or one value per utterance (any sequence takes the per-utterance kernels and adds
@@ -735,6 +768,10 @@ class AcousticEngine:
         Column 6 of a Span's block is the frames the Span occupies after the curves; with the frames of the phonemes in front of it
         (``durations``) that tells which samples carry the emphasised word.  A zero entry inside a Span scaled below 1 becomes
         mean * (1 - scale), as the reference's _scale_variance does for a whole call;
+        prosody_fit: None, or per utterance None / a prosody_fit.Fit / a list of span Fits (prosody_fit.resolve_fits; DESIGN.md
+        section 22): the utterance, its pauses or the span take exactly the target's frames.  The result then has ``prosody_stats``
+        and ``prosody_fit`` = dict(report=per utterance [n_u, 8] (columns prosody_fit.FIT_COLUMNS), scales=[B, 4], extra=per
+        utterance int32 [L_u]);
         z_noise: optional list of [80, T_u] tensors = 0.8*N(0,1) (Glow.py:363) - drawn on the device if omitted.
         Returns dict(mel=[list of [T'_u,80]], durations, pitch, energy, plus packed tensors).
 
@@ -745,12 +782,13 @@ class AcousticEngine:
             with torch.cuda.device(self.device):  # launches go to streams of self.device: it must be the current HIP device
                 return self.forward(texts, utt_embs, lang_ids, durations, pitch, energy, z_noise, duration_scaling_factor,
                                     pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor, run_postflow, taps, generator,
-                                    prosody_curves)
+                                    prosody_curves, prosody_fit)
         ops, dev = self.ops, self.device
         B = len(texts)
         Ls = [int(t.shape[0]) for t in texts]
         curves = prosody.resolve_curves(Ls, prosody_curves)
-        if curves is not None:
+        segments = prosody_fit_mod.resolve_fits(Ls, prosody_fit)
+        if curves is not None or segments is not None:
             table = prosody.broadcast_scales(B, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor)
         else:
             table = prosody.resolve_scales(B, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor)
@@ -768,8 +806,25 @@ class AcousticEngine:
             lang_idx = torch.tensor([int(i) for i in lang_ids], dtype=torch.int32).to(dev)
         gp, ge, gd = packed_gold(pitch, torch.float32), packed_gold(energy, torch.float32), packed_gold(durations, torch.int32)
         graphs = self.use_graphs and taps is None and dev.type == "cuda"
-        stats = span_stats = None
-        if curves is not None:  # per-phoneme curves: the table, the scales and the span ranges are inputs of the captured graph
+        stats = span_stats = fit_out = None
+        if segments is not None:  # time budgets: the segment tables are inputs of the captured graph beside the scales and the curves
+            ctab, ranges, span_counts = curves if curves is not None else (None, None, None)
+            n = 0 if ranges is None else int(ranges.shape[0])
+            rows_host, spec_host = prosody_fit_mod.device_tables(segments)
+            fit_spans = bool((segments[:, 1] == prosody_fit_mod.SPAN).any())
+            ins = dict(scales=None if table is None else torch.from_numpy(table).to(dev), curves=None if ctab is None else torch.from_numpy(ctab).to(dev),
+                       ranges=torch.from_numpy(np.ascontiguousarray(ranges.T)).to(dev) if n else None,
+                       seg_rows=torch.from_numpy(rows_host).to(dev), seg_spec=torch.from_numpy(spec_host).to(dev))
+            if graphs:
+                key = ("A", tuple(Ls), lang_idx is not None, gp is not None, ge is not None, gd is not None, "fit", table is not None, ctab is not None, n,
+                       int(segments.shape[0]), fit_spans)
+                ins.update(text=text, emb=emb, lang_idx=lang_idx, gold_p=gp, gold_e=ge, gold_d=gd)
+                res = self._graphs.run(key, ins, lambda **kw: self._stage_a(rag_p=rag_p, rag_b=rag_b, fit_spans=fit_spans, **kw))
+            else:
+                res = self._stage_a(text, emb, lang_idx, gp, ge, gd, rag_p, rag_b, taps=taps, fit_spans=fit_spans, **ins)
+            enc, p, en, d, stats, span_stats = res[:6]
+            fit_out = res[6:]
+        elif curves is not None:  # per-phoneme curves: the table, the scales and the span ranges are inputs of the captured graph
             ctab, ranges, span_counts = curves
             n = int(ranges.shape[0])
             ins = dict(scales=None if table is None else torch.from_numpy(table).to(dev), curves=torch.from_numpy(ctab).to(dev),
@@ -837,6 +892,9 @@ class AcousticEngine:
         if span_stats is not None:
             span_stats = span_stats.cpu().numpy()
             out["prosody_span_stats"] = prosody.split_span_stats((span_stats[0], span_stats[1]), span_counts)
+        if fit_out is not None:
+            report, solved, extra = (t.cpu().numpy() for t in fit_out)
+            out["prosody_fit"] = prosody_fit_mod.result(report, solved, extra, segments, Ls)
         return out
 
     @torch.inference_mode()

@@ -12,6 +12,7 @@ script written against the reference (run_text_to_file_reader.py:8-16) works unc
 * additive API: ``synthesize_batch`` (ragged batches, optionally sharded over the ranks of torch.distributed; every prosody scale
   a scalar or one value per utterance), ``synthesize_grid`` (one text over a grid of prosody scales, with the statistics of what
   each scale did), ``prosody_curves=`` / ``curves=`` (per-phoneme prosody curves: stress one word, prosody.emphasis),
+  ``prosody_fit=`` (an utterance, its pauses or a span of phonemes in exactly N frames or seconds: prosody_fit.Fit),
   ``evaluate_against_recordings`` (synthesise and measure against recordings of the same sentences: MCD along a DTW path and
   the F0 errors, compare.py), ``check_pronunciation`` / ``synthesize_grid(check_pronunciation=True)`` (synthesise and ask the aligner
   whether the waveform still says the text, without a recording: phoneme error rate of the decoded CTC posteriors and per-phoneme
@@ -33,6 +34,7 @@ import numpy as np
 import torch
 
 from . import engine, prosody
+from . import prosody_fit as prosody_fit_mod
 from .phonemes import ArticulatoryCombinedTextFrontend, get_language_id
 from .ragged import Ragged
 
@@ -168,6 +170,7 @@ class ToucanTTSInterface(torch.nn.Module):
         self._style = None
         self.last_prosody_stats = None  # (before, after) of the last batch that took per-utterance prosody scales or curves
         self.last_prosody_span_stats = None  # per utterance (before, after) of its Spans, of the last batch that took prosody curves
+        self.last_prosody_fit = None  # dict(report, scales, extra) of the last batch that took time budgets (prosody_fit.py)
         self.last_delivery = None  # float64 [B, 8] on the device (truepeak.DELIVERY_COLUMNS) of the last call that took true_peak_ceiling= / limiter=
         self.last_loudness = None  # float64 [B, 8] on the device (loudness.LOUDNESS_COLUMNS) of the last call that took loudness=
         self.last_speech_activity = None  # (stats [B, 8], runs [B, 64, 2], counts [B, 16]) on the device of the last call that took speech_level=
@@ -243,13 +246,16 @@ class ToucanTTSInterface(torch.nn.Module):
                 peak_ceiling=-1.0,
                 speech_level=None,
                 true_peak_ceiling=None,
-                limiter=False):
+                limiter=False,
+                prosody_fit=None):
         """The reference's signature (ToucanTTSInterface.py:132-143) plus additive keywords.  ``z_noise`` [80, T]: the PostFlow
         noise 0.8 N(0,1) the reference draws inside the model (Glow.py:363), so that a call can be reproduced and checked
         against the oracle; None draws it on the device.  ``sample_rate`` / ``pcm16``: the waveform at another rate than 24 kHz
         and / or as int16, converted on the device (resample.py); the figure of ``view`` keeps drawing the 24 kHz wave.
         ``prosody_curves``: this utterance's per-phoneme curves, an [L, 5] array or a list of ``prosody.Span`` (as one entry of
-        ``synthesize_batch``'s keyword, documented there); None is the call as it was.  ``loudness`` / ``peak_ceiling``: as in
+        ``synthesize_batch``'s keyword, documented there); None is the call as it was.  ``prosody_fit``: a ``prosody_fit.Fit`` (this
+        utterance in a given number of frames or seconds) or a list of span ``Fit``s, as one entry of ``synthesize_batch``'s keyword;
+        None is the call as it was.  ``loudness`` / ``peak_ceiling``: as in
         ``synthesize_batch``; the figure of ``view`` then draws the normalised 24 kHz wave.  ``speech_level``, ``true_peak_ceiling`` / ``limiter``: as in
         ``synthesize_batch``."""
         self._check_output_format(sample_rate, pcm16)
@@ -259,6 +265,9 @@ class ToucanTTSInterface(torch.nn.Module):
         with torch.inference_mode():
             phones = self.text2phone.string_to_tensor(text, input_phonemes=input_is_phones)
             curves = {} if prosody_curves is None else dict(prosody_curves=[prosody_curves])
+            if prosody_fit is not None:
+                prosody_fit_mod.resolve_fits([int(phones.shape[0])], [prosody_fit])  # (ValueError before anything runs)
+                curves["prosody_fit"] = [prosody_fit]
             wav24, spans = self._synthesize_packed([phones], [self.default_utterance_embedding], [self._lang()],
                                                    z_noise=None if z_noise is None else [z_noise],
                                                    durations=None if durations is None else [durations],
@@ -294,6 +303,7 @@ class ToucanTTSInterface(torch.nn.Module):
             self.last_mel = out["mel"]
             self.last_prosody_stats = out.get("prosody_stats")
             self.last_prosody_span_stats = out.get("prosody_span_stats")
+            self.last_prosody_fit = out.get("prosody_fit")
             return out["wav"], out["wav_spans"]
         out = self.phone2mel.forward(phones, emb, lang_ids, z_noise=z_noise, **kw)
         wav, rag = self.mel2wav.forward(out["mel_packed"], out["rag_mel"])
@@ -301,6 +311,7 @@ class ToucanTTSInterface(torch.nn.Module):
         self.last_mel = out["mel"]
         self.last_prosody_stats = out.get("prosody_stats")
         self.last_prosody_span_stats = out.get("prosody_span_stats")
+        self.last_prosody_fit = out.get("prosody_fit")
         return wav, list(zip(rag.begins, rag.lengths))
 
     def _synthesize(self, phones, embs, langs, z_noise=None, sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None,
@@ -421,7 +432,7 @@ class ToucanTTSInterface(torch.nn.Module):
     def synthesize_batch(self, texts, input_is_phones=True, utterance_embeddings=None, z_noise=None, durations=None, pitch=None,
                          energy=None, duration_scaling_factor=1.0, pitch_variance_scale=1.0, energy_variance_scale=1.0,
                          pause_duration_scaling_factor=1.0, distributed=False, sample_rate=None, pcm16=False, prosody_curves=None,
-                         loudness=None, peak_ceiling=-1.0, speech_level=None, true_peak_ceiling=None, limiter=False):
+                         loudness=None, peak_ceiling=-1.0, speech_level=None, true_peak_ceiling=None, limiter=False, prosody_fit=None):
         """Additive API: a ragged batch in one pass; each utterance equals the reference run on it alone (16-bit configurations: bit
         for bit whatever the batch; fp32: durations / pitch / energy bit for bit, the mel to fp32 rounding order - DESIGN.md section 4).
         texts: phoneme strings (or [L,62] feature tensors).  durations / pitch / energy: optional per-utterance gold prosody (the
@@ -447,6 +458,19 @@ class ToucanTTSInterface(torch.nn.Module):
         frames in front of it (``self.last_durations``) tells which samples carry the emphasised word.  ValueError for a wrong
         shape, a Span outside its utterance, a value that is not finite or a duration factor that is not positive (the message
         names the utterance and the phoneme), and for curves with ``distributed=True``.
+        ``prosody_fit``: None (the call as it was: the same entry, the same bits), or a list with one entry per utterance - None, a
+        ``prosody_fit.Fit`` or a list of span ``Fit``s.  ``Fit(target_frames=N)`` / ``Fit(target_seconds=3.2)`` gives the utterance
+        exactly that many mel frames (384 samples each) by solving for its duration scale on the device, between the predictors and
+        the control kernel of the same pass; ``knob="pause"`` keeps the speech tempo and lets the pauses absorb the slot;
+        ``Fit(..., start=a, stop=b)`` fits phonemes [a, b) alone.  Where no scale reaches the target (the frame count is a step
+        function of the scale) ``exact=True`` hands the missing frames to the phonemes next in line, evenly spread; ``exact=False``
+        takes the nearest scale.  It composes with the scales, ``prosody_curves`` and gold ``durations``: the fit varies its one
+        knob, everything else stays as given.  ``self.last_prosody_fit`` = dict(report: per utterance [n_u, 8] with the columns
+        ``prosody_fit.FIT_COLUMNS`` (status: ``prosody_fit.STATUS``; a target outside the knob's bounds is reported CLAMPED, not
+        raised), scales: the solved [B, 4] table, extra: per utterance the frames handed out); ``self.last_prosody_stats`` is
+        filled as above.  ValueError (the message names the utterance and the segment) for both or neither target, a target that is
+        no whole number of frames in 1 .. 2^24, bad bounds, a span outside its utterance, overlapping spans, a whole-utterance Fit
+        beside spans, and with ``distributed=True``.
         ``loudness``: None (the call as it was: no launch, the same bits) or a target in LUFS, e.g. -23 (EBU R 128).  Every
         utterance's integrated loudness after ITU-R BS.1770-4 (K-weighting, 400 ms blocks, absolute gate at -70 LUFS, relative gate
         at -10 LU) is measured at 24 kHz on the device and the utterance scaled by one gain to the target, before the conversion of
@@ -491,6 +515,8 @@ class ToucanTTSInterface(torch.nn.Module):
             raise ValueError("per-utterance prosody scales are not available with distributed=True: the sharded deal carries scalars")
         if distributed and prosody_curves is not None:
             raise ValueError("prosody curves are not available with distributed=True: the sharded deal carries scalars")
+        if distributed and prosody_fit is not None:
+            raise ValueError("prosody_fit is not available with distributed=True: the sharded deal carries scalars")
         feats = [t if torch.is_tensor(t) else self.text2phone.string_to_tensor(t, input_phonemes=input_is_phones) for t in texts]
         embs = utterance_embeddings if utterance_embeddings is not None else [self.default_utterance_embedding] * len(feats)
         kw = dict(duration_scaling_factor=duration_scaling_factor, pitch_variance_scale=pitch_variance_scale,
@@ -499,6 +525,9 @@ class ToucanTTSInterface(torch.nn.Module):
             if prosody_curves is not None:
                 prosody.resolve_curves([int(f.shape[0]) for f in feats], prosody_curves)  # (ValueError before anything runs)
                 kw["prosody_curves"] = prosody_curves
+            if prosody_fit is not None:
+                prosody_fit_mod.resolve_fits([int(f.shape[0]) for f in feats], prosody_fit)  # (ValueError before anything runs)
+                kw["prosody_fit"] = prosody_fit
             with torch.inference_mode():
                 return self._synthesize(feats, embs, [self._lang()] * len(feats), z_noise=z_noise, durations=durations, pitch=pitch,
                                         energy=energy, sample_rate=sample_rate, pcm16=pcm16, loudness=loudness, peak_ceiling=peak_ceiling,
@@ -760,6 +789,8 @@ class ToucanTTSInterface(torch.nn.Module):
             raise ValueError("stream() cannot normalise loudness: the integrated loudness needs the whole utterance; use forward(loudness=...)")
         if speech_level is not None:
             raise ValueError("stream() cannot normalise the speech level: the active speech level needs the whole utterance; use forward(speech_level=...)")
+        if prosody.get("prosody_fit") is not None:
+            raise ValueError("stream() does not take prosody_fit; use forward(prosody_fit=...)")
         from . import streaming
         convert = self._check_output_format(sample_rate, pcm16)
         halo = streaming.DEFAULT_HALO if halo_frames is None else halo_frames

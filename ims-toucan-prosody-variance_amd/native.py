@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import capi, engine, packing, prosody
+from . import prosody_fit as prosody_fit_mod
 from .ragged import Ragged
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 4}
@@ -51,6 +52,7 @@ class NativePipeline:
         self._streams = None  # (acoustic, vocoder) stream pair of forward_pipelined, made on first use
         self._prosody_stats = None  # (before, after) of the last stage A that took per-utterance scales or curves
         self._prosody_span_stats = None  # per utterance (before, after) of its Spans, of the last stage A that took curves
+        self._prosody_fit = None  # report / solved scales / extra frames of the last stage A that took time budgets
         if vocoder_sd is not None:
             assert vocoder_kind in ("hifigan", "bigvgan")
             voc = engine.VocoderEngine(vocoder_sd, vocoder_kind, "cpu", precision=self.vocoder_precision, pack_only=True)
@@ -282,14 +284,15 @@ class NativePipeline:
             z_sq[b0:b0 + n].copy_(torch.as_tensor(zu, dtype=torch.float32).t()[: 2 * n].reshape(n, 160))
         return z_sq
 
-    def _stage_a(self, packed, duration_scale, pitch_scale, energy_scale, pause_scale, st, prosody_curves=None):
+    def _stage_a(self, packed, duration_scale, pitch_scale, energy_scale, pause_scale, st, prosody_curves=None, prosody_fit=None):
         """Stage A on a packed batch (tts_encoder, tts_variance_predictors, tts_control_and_regulate - or its _v form when a scale is a
-        sequence: one value per utterance, scalars among them broadcast - or its _c form with per-phoneme curves): mel frames per
-        utterance."""
+        sequence: one value per utterance, scalars among them broadcast - or its _c form with per-phoneme curves - or its _t form
+        with time budgets): mel frames per utterance."""
         lib, Ls = self.lib, packed["Ls"]
         B = len(Ls)
         curves = prosody.resolve_curves(Ls, prosody_curves)  # (ValueError before anything is enqueued)
-        if curves is not None:
+        segments = prosody_fit_mod.resolve_fits(Ls, prosody_fit)
+        if curves is not None or segments is not None:
             table = prosody.broadcast_scales(B, duration_scale, pitch_scale, energy_scale, pause_scale)
         else:
             table = prosody.resolve_scales(B, duration_scale, pitch_scale, energy_scale, pause_scale)
@@ -297,9 +300,18 @@ class NativePipeline:
         capi.check(lib.tts_encoder(self.h, ptr(packed["text"]), ptr(packed["emb"]), ptr(packed["lang"]), (C.c_int32 * B)(*Ls), B, st), "tts_encoder")
         capi.check(lib.tts_variance_predictors(self.h, ptr(packed["gp"]), ptr(packed["ge"]), ptr(packed["gd"]), st), "tts_variance_predictors")
         frames = (C.c_int32 * B)()
-        self._prosody_stats = self._prosody_span_stats = None
+        self._prosody_stats = self._prosody_span_stats = self._prosody_fit = None
         fptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        if curves is not None:  # per-phoneme curves (include/toucan_prosody_curves.h)
+        if segments is not None:  # time budgets (include/toucan_prosody_fit.h), with or without curves
+            ctab, ranges, counts = curves if curves is not None else (None, None, None)
+            n = 0 if ranges is None else int(ranges.shape[0])
+            capi.check(lib.tts_control_and_regulate_t(self.h, fptr(table), fptr(ctab), fptr(ranges) if n else None, n, fptr(segments),
+                                                      int(segments.shape[0]), frames, st), "tts_control_and_regulate_t")
+            report = np.empty((int(segments.shape[0]), capi.FIT_N_COLUMNS), dtype=np.float32)
+            solved, extra = np.empty((B, capi.PROSODY_SCALES), dtype=np.float32), np.empty(sum(Ls), dtype=np.int32)
+            capi.check(lib.tts_copy_prosody_fit(self.h, fptr(report), fptr(solved), fptr(extra), st), "tts_copy_prosody_fit")
+            self._prosody_fit = prosody_fit_mod.result(report, solved, extra, segments, Ls)
+        elif curves is not None:  # per-phoneme curves (include/toucan_prosody_curves.h)
             ctab, ranges, counts = curves
             n = int(ranges.shape[0])
             capi.check(lib.tts_control_and_regulate_c(self.h, fptr(table), fptr(ctab), fptr(ranges) if n else None, n, frames, st),
@@ -323,27 +335,27 @@ class NativePipeline:
     @torch.inference_mode()
     def forward(self, texts, utt_embs, lang_ids=None, durations=None, pitch=None, energy=None, z_noise=None, duration_scaling_factor=1.0,
                 pitch_variance_scale=1.0, energy_variance_scale=1.0, pause_duration_scaling_factor=1.0, run_postflow=True, vocode=True,
-                generator=None, packed=None, z_sq=None, prosody_curves=None):
+                generator=None, packed=None, z_sq=None, prosody_curves=None, prosody_fit=None):
         """Same arguments and result keys as engine.AcousticEngine.forward (+ ``wav`` / ``wav_spans`` when a vocoder is loaded and
-        ``vocode``; ``prosody_stats`` when a scale is a sequence; ``prosody_stats`` and ``prosody_span_stats`` with ``prosody_curves``,
-        documented there).  Every stage is one call into libtoucan_hip.so."""
+        ``vocode``; ``prosody_stats`` when a scale is a sequence; ``prosody_stats`` and ``prosody_span_stats`` with ``prosody_curves``;
+        ``prosody_stats`` and ``prosody_fit`` with ``prosody_fit``, documented there).  Every stage is one call into libtoucan_hip.so."""
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
                 return self.forward(texts, utt_embs, lang_ids, durations, pitch, energy, z_noise, duration_scaling_factor, pitch_variance_scale,
                                     energy_variance_scale, pause_duration_scaling_factor, run_postflow, vocode, generator, packed, z_sq,
-                                    prosody_curves)
+                                    prosody_curves, prosody_fit)
         dev, lib, st = self.device, self.lib, self._stream()
         assert np.ndim(duration_scaling_factor) > 0 or duration_scaling_factor > 0  # (a sequence is checked per utterance in _stage_a)
         if packed is None:
             packed = self.pack_inputs(texts, utt_embs, lang_ids, durations, pitch, energy)
         Ls = packed["Ls"]
         Ts = self._stage_a(packed, duration_scaling_factor, pitch_variance_scale, energy_variance_scale, pause_duration_scaling_factor, st,
-                           prosody_curves)
+                           prosody_curves, prosody_fit)
         if max(Ts) > self._pmax:  # longer than the position table: enlarge it and redo the (cheap) phoneme stages
             self._ensure_pe(max(Ts))
             return self.forward(texts, utt_embs, lang_ids, durations, pitch, energy, z_noise, duration_scaling_factor, pitch_variance_scale,
                                 energy_variance_scale, pause_duration_scaling_factor, run_postflow, vocode, generator, packed, z_sq,
-                                prosody_curves)
+                                prosody_curves, prosody_fit)
         rag_p = Ragged(Ls, dev)
         rag_f = Ragged(Ts, dev, align=2)
         capi.check(lib.tts_decoder(self.h, st), "tts_decoder")
@@ -373,6 +385,8 @@ class NativePipeline:
             out["prosody_stats"] = self._prosody_stats
         if self._prosody_span_stats is not None:
             out["prosody_span_stats"] = self._prosody_span_stats
+        if self._prosody_fit is not None:
+            out["prosody_fit"] = self._prosody_fit
         out["mel"] = [mel_packed[b0:b0 + n] for b0, n in zip(rag_out.begins, rag_out.lengths)]
         for key, src in (("durations", d), ("pitch", p), ("energy", en)):
             out[key] = [src[b0:b0 + n] for b0, n in zip(rag_p.begins, rag_p.lengths)]
