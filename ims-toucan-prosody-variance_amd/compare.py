@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import capi
+from .ragged import begins, plan_bp_store
 
 SR, HOP, N_MELS = 16000, 256, capi.COMPARE_MELS
 MAX_FRAMES = capi.DTW_MAX_FRAMES  # per side of a pair: 65 s
@@ -62,9 +63,9 @@ def plan_launches(frames_a, frames_b, force_scratch=False, max_scratch_bytes=MAX
     """[(first pair, one past the last)]: consecutive pairs whose scratch back-pointers stay within max_scratch_bytes per launch.
     (A single pair needs at most 4 MiB; every launch takes at least one pair.)"""
     plans, lo, held = [], 0, 0
-    for p, (ta, tb) in enumerate(zip(frames_a, frames_b)):
-        need = bp_bytes(ta, tb)
-        need = need if force_scratch or need > LDS_BP_BYTES else 0
+    needs = [bp_bytes(ta, tb) for ta, tb in zip(frames_a, frames_b)]
+    for p, off in enumerate(plan_bp_store(needs, LDS_BP_BYTES, force_scratch)[0]):
+        need = needs[p] if off >= 0 else 0
         if held > 0 and held + need > max_scratch_bytes:
             plans.append((lo, p))
             lo, held = p, 0
@@ -100,10 +101,6 @@ def finalise(sums, path_length, with_f0=True):
     return out
 
 
-def _begins(counts):
-    return [int(b) for b in np.concatenate([[0], np.cumsum(counts)[:-1]])] if len(counts) else []
-
-
 def waves_to_16k(owner, waves, srs, names, tracked=False):
     """Mono float32 waves at their rates -> at 16 kHz (device resampler), each divided by its peak: the one route from a wave to
     the 16 kHz front ends (SpeechComparator, pronunciation.PronunciationChecker).  owner: holds ``device`` and ``_resampler`` (None
@@ -131,7 +128,7 @@ def waves_to_16k(owner, waves, srs, names, tracked=False):
         if owner._resampler is None:
             owner._resampler = resample.Resampler(owner.device)
         packed = torch.from_numpy(np.concatenate([out[p] for p in which])).to(owner.device)
-        y, spans = owner._resampler.resample(packed, list(zip(_begins([len(out[p]) for p in which]), [len(out[p]) for p in which])), sr, SR)
+        y, spans = owner._resampler.resample(packed, list(zip(begins([len(out[p]) for p in which]), [len(out[p]) for p in which])), sr, SR)
         y = y.cpu().numpy()
         for p, (b, n) in zip(which, spans):
             out[p] = y[b:b + n].copy()
@@ -187,21 +184,16 @@ class SpeechComparator:
         """(host table, device room for it, scratch bytes, LDS bytes, path entries, path begins).  force_scratch None: no store."""
         B = len(frames_a)
         table = (capi.TtsDtwPair * B)()
-        ba, bb = _begins(frames_a), _begins(frames_b)
-        pb = _begins([ta + tb - 1 for ta, tb in zip(frames_a, frames_b)])
-        total = lds = 0
+        ba, bb = begins(frames_a), begins(frames_b)
+        pb = begins([ta + tb - 1 for ta, tb in zip(frames_a, frames_b)])
+        off, total, lds = [-1] * B, 0, 0
+        if force_scratch is not None:
+            off, total, lds = plan_bp_store([bp_bytes(ta, tb) for ta, tb in zip(frames_a, frames_b)], LDS_BP_BYTES, force_scratch)
         for p in range(B):
-            need = bp_bytes(frames_a[p], frames_b[p])
-            off = -1
-            if force_scratch is not None:
-                if force_scratch or need > LDS_BP_BYTES:
-                    off, total = total, total + need
-                else:
-                    lds = max(lds, need)
-            table[p] = capi.TtsDtwPair(ba[p], int(frames_a[p]), bb[p], int(frames_b[p]), off, pb[p])
+            table[p] = capi.TtsDtwPair(ba[p], int(frames_a[p]), bb[p], int(frames_b[p]), off[p], pb[p])
         dev = torch.empty(max(B, 1) * 32, dtype=torch.uint8, device=self.device)
         entries = int(sum(frames_a) + sum(frames_b) - B)
-        return table, dev, total, (lds + 15) // 16 * 16, entries, pb
+        return table, dev, total, lds, entries, pb
 
     def _check_cepstra(self, cep, frames, side):
         assert cep.dtype == torch.float32 and cep.is_contiguous() and cep.device == self.device, f"side {side}: float32 cepstra on {self.device}"
@@ -265,7 +257,7 @@ class SpeechComparator:
         entries = sum(frames_a) + sum(frames_b) - len(frames_a)
         host = np.zeros((max(entries, 1), 2), dtype=np.int32)
         lens = []
-        for p, (b, pts) in enumerate(zip(_begins([ta + tb - 1 for ta, tb in zip(frames_a, frames_b)]), paths)):
+        for p, (b, pts) in enumerate(zip(begins([ta + tb - 1 for ta, tb in zip(frames_a, frames_b)]), paths)):
             pts = np.asarray(pts, dtype=np.int32).reshape(-1, 2)
             if not 1 <= len(pts) <= frames_a[p] + frames_b[p] - 1:
                 raise ValueError(f"pair {p}: a path of {len(pts)} points for {frames_a[p]} x {frames_b[p]} frames")
@@ -332,7 +324,7 @@ class SpeechComparator:
         validate_pairs(frames_a, frames_b)
         f0_a, f0_b = self._tracks(f0, a16, b16, frames_a, frames_b)
         cep_a, cep_b = cep[:sum(frames_a)], cep[sum(frames_a):]
-        ra, rb = _begins(frames_a) + [sum(frames_a)], _begins(frames_b) + [sum(frames_b)]
+        ra, rb = begins(frames_a) + [sum(frames_a)], begins(frames_b) + [sum(frames_b)]
         held = []
         for lo, hi in plan_launches(frames_a, frames_b, max_scratch_bytes=self.max_scratch_bytes):
             ca, cb, fa, fb = cep_a[ra[lo]:ra[hi]], cep_b[rb[lo]:rb[hi]], frames_a[lo:hi], frames_b[lo:hi]

@@ -129,9 +129,6 @@ int lstm_step(const float* xproj, int ldx, const float* w_hh_blk, const float* h
 // the output itself by thread 0.
 constexpr int MAS_THREADS = 256;
 
-// log correctly rounded to float32 (through double): the one transcendental on the path, kept independent of libm's float32 form
-__device__ inline float log_rn(float x) { return (float)log((double)x); }
-
 __device__ inline float block_max(float v, float* red) {
   const int tid = threadIdx.x;
   red[tid] = v;

@@ -180,6 +180,9 @@ __device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
+// log correctly rounded to float32 (through double), independent of libm's float32 form
+__device__ inline float log_rn(float x) { return (float)log((double)x); }
+
 // Glow, reverse pass: the expressions that more than one kernel evaluates, in one place each so that every kernel contracts and
 // rounds them alike (the coupling: tts_conv1d's epilogue and wavenet_block_kernel; the mix: glow_mix_kernel and wavenet_block_kernel).
 //   coupling (Glow.py:301): x1 = (x1 - m) exp(-logs), m and logs with their biases already added

@@ -7,6 +7,7 @@
 // Batch independence: every kernel computes a pair (a row) in an order that depends on that pair alone; the reductions are fixed
 // trees, there are no atomics and no workgroup waits on another one.
 #include "common.h"
+#include "pair_sweep.h"
 #include "../../include/toucan_compare.h"
 
 namespace tts {
@@ -80,14 +81,11 @@ int mel_cepstra(const float* logmel, int ld, int n_src_rows, const int* src_row,
 }
 
 // ---- dynamic time warping, one workgroup per pair ----------------------------------------------------------------------------
-// The rows are taken in bands of 256: in a band thread t owns row i = band + t and keeps a[i] in registers; at step s of the band's
-// anti-diagonal sweep it forms the cell (i, s - t), so b[j] streams (the next row of b is loaded a step ahead).  D of the last two
-// anti-diagonals lies in LDS (diag[2][256], fp64): D(i-1, j) is what thread t - 1 wrote a step ago, D(i-1, j-1) is what this thread
-// read there a step ago and kept, D(i, j-1) is its own last value.  Thread 0 takes both from row[], D of the previous band's last
-// row, which thread 255 overwrites 255 columns behind thread 0's reads.  Back-pointers: 2 bits per cell (0 diagonal, 1 up, 2 left),
-// a thread collecting 16 of its row in a register before it stores the word - to LDS or to the caller's scratch.  Thread 0 then
-// walks back from the last cell into row[] (free by then) and the workgroup writes the path forwards.
-constexpr int D_THREADS = 256;
+// The sweep of pair_sweep.h over fp64 costs: thread t keeps a[i] in registers and b[j] streams (the next row of b is loaded a step
+// ahead); a cell adds its distance d to the chosen predecessor, which does not exist outside the matrix (infinite borders; cell
+// (0, 0) is d alone).  Thread 0 then walks back from the last cell into row[] (free by then) and the workgroup writes the path
+// forwards.
+constexpr int D_THREADS = SWEEP_THREADS;
 constexpr int D_MAX = TTS_DTW_MAX_FRAMES;
 constexpr int D_ROW_BYTES = D_MAX * 8;                 // row[]: fp64 D of a band's last row; then the path, one 32-bit word per point
 constexpr int D_DIAG_BYTES = 2 * D_THREADS * 8;
@@ -95,7 +93,48 @@ constexpr int D_FIXED_BYTES = D_ROW_BYTES + D_DIAG_BYTES + 16;  // + one slot fo
 static_assert(2 * D_MAX - 1 <= D_ROW_BYTES / 4, "the path fits where the band row was");
 static_assert(D_FIXED_BYTES % 16 == 0 && D_FIXED_BYTES + TTS_DTW_LDS_BP_BYTES <= 160 * 1024, "LDS budget");
 
-__host__ __device__ inline long long dtw_bp_words(int ta, int tb) { return (long long)ta * ((tb + 15) >> 4); }
+template <int KP>
+struct DtwCells {
+  using value_t = double;
+  static constexpr int ORIGIN = 0;
+  const float *A, *B;
+  int K, Tb;
+  double* cost;
+  float av[KP], bn[KP], bc[KP];  // a[i]; b of the next step and of this one
+
+  __device__ __forceinline__ void band(int i, bool active) {
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      av[k] = (active && k < K) ? A[(size_t)i * K + k] : 0.0f;
+      bn[k] = (active && threadIdx.x == 0 && k < K) ? B[k] : 0.0f;  // thread 0 starts at step 0 with b[0]
+    }
+  }
+  __device__ __forceinline__ double border(int, int) const { return __builtin_huge_val(); }
+  __device__ __forceinline__ void step(int j, bool active) {
+#pragma unroll
+    for (int k = 0; k < KP; ++k) bc[k] = bn[k];
+    const int jn = j + 1;  // the row of b for the next step, loaded now
+    if (active && jn >= 0 && jn < Tb) {
+#pragma unroll
+      for (int k = 0; k < KP; ++k)
+        if (k < K) bn[k] = B[(size_t)jn * K + k];
+    }
+  }
+  __device__ __forceinline__ double via(unsigned int, double pred, int) const { return pred; }
+  __device__ __forceinline__ double cell(int i, int j, double best) const {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      if (k < K) {
+        const double df = (double)av[k] - (double)bc[k];
+        acc += df * df;
+      }
+    }
+    const double d = sqrt(acc);
+    return (i == 0 && j == 0) ? d : d + best;
+  }
+  __device__ __forceinline__ void last(double D) const { *cost = D; }
+};
 
 template <int KP>
 __global__ __launch_bounds__(D_THREADS) void dtw_kernel(const float* __restrict__ cep_a, const float* __restrict__ cep_b, int K,
@@ -108,83 +147,15 @@ __global__ __launch_bounds__(D_THREADS) void dtw_kernel(const float* __restrict_
   const int p = blockIdx.x, tid = threadIdx.x;
   const TtsDtwPair pr = pairs[p];
   const int Ta = pr.frames_a, Tb = pr.frames_b, W = (Tb + 15) >> 4;
-  const float* A = cep_a + (size_t)pr.begin_a * K;
-  const float* B = cep_b + (size_t)pr.begin_b * K;
-  const bool in_lds = pr.scratch_off < 0;
-  unsigned int* bp = in_lds ? reinterpret_cast<unsigned int*>(lds + D_FIXED_BYTES) : reinterpret_cast<unsigned int*>(scratch + pr.scratch_off);
-  const double inf = __builtin_huge_val();
-
-  for (int i0 = 0; i0 < Ta; i0 += D_THREADS) {
-    const int i = i0 + tid;
-    const bool active = i < Ta;
-    const bool feeds_next = tid == D_THREADS - 1 && i0 + D_THREADS < Ta;  // this row is the next band's row[]
-    const int steps = min(D_THREADS, Ta - i0) + Tb - 1;
-    float av[KP], bn[KP];
-#pragma unroll
-    for (int k = 0; k < KP; ++k) {
-      av[k] = (active && k < K) ? A[(size_t)i * K + k] : 0.0f;
-      bn[k] = (active && tid == 0 && k < K) ? B[k] : 0.0f;  // thread 0 starts at step 0 with b[0]
-    }
-    double left = inf, kept_up = inf;
-    unsigned int word = 0;
-    unsigned int* bp_row = bp + (size_t)i * W;
-    for (int s = 0; s < steps; ++s) {
-      const int j = s - tid;
-      const bool cell = active && j >= 0 && j < Tb;
-      float bc[KP];
-#pragma unroll
-      for (int k = 0; k < KP; ++k) bc[k] = bn[k];
-      const int jn = j + 1;  // the row of b for the next step, loaded now
-      if (active && jn >= 0 && jn < Tb) {
-#pragma unroll
-        for (int k = 0; k < KP; ++k)
-          if (k < K) bn[k] = B[(size_t)jn * K + k];
-      }
-      if (cell) {
-        const double up = tid == 0 ? (i0 == 0 ? inf : row[j]) : diag[((s - 1) & 1) * D_THREADS + tid - 1];
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-          if (k < K) {
-            const double df = (double)av[k] - (double)bc[k];
-            acc += df * df;
-          }
-        }
-        const double d = sqrt(acc);
-        double best = kept_up;  // D(i-1, j-1)
-        unsigned int code = 0;
-        if (up < best) {
-          best = up;
-          code = 1;
-        }
-        if (left < best) {
-          best = left;
-          code = 2;
-        }
-        const double D = (i == 0 && j == 0) ? d : d + best;
-        kept_up = up;
-        left = D;
-        diag[(s & 1) * D_THREADS + tid] = D;
-        if (feeds_next) row[j] = D;
-        word |= code << (2 * (j & 15));
-        if ((j & 15) == 15 || j == Tb - 1) {
-          bp_row[j >> 4] = word;
-          word = 0;
-        }
-        if (i == Ta - 1 && j == Tb - 1) cost[p] = D;
-      }
-      __syncthreads();
-    }
-  }
-  if (!in_lds) __threadfence_block();
-  __syncthreads();
+  DtwCells<KP> cells = {cep_a + (size_t)pr.begin_a * K, cep_b + (size_t)pr.begin_b * K, K, Tb, cost + p};
+  const unsigned int* bp = pair_sweep(cells, Ta, Tb, row, diag, pr.scratch_off, lds + D_FIXED_BYTES, scratch);
   unsigned int* points = reinterpret_cast<unsigned int*>(lds);  // row[] is free: the path backwards, (i << 16) | j
   if (tid == 0) {
     int i = Ta - 1, j = Tb - 1, n = 0;
     for (;;) {
       points[n++] = ((unsigned int)i << 16) | (unsigned int)j;
       if (i == 0 && j == 0) break;
-      unsigned int code = (bp[(size_t)i * W + (j >> 4)] >> (2 * (j & 15))) & 3u;
+      unsigned int code = bp_code(bp, W, i, j);
       if (i == 0) code = 2;       // (what the sweep stored there anyway: no other neighbour exists)
       else if (j == 0) code = 1;
       if (code == 0) {
@@ -223,14 +194,7 @@ int upload_pairs(const char* what, const TtsDtwPair* host, TtsDtwPair* dev, int 
                   "%s: pair %d: its path slot (%lld + %d) lies outside the %lld path entries", what, p, (long long)q.path_begin,
                   q.frames_a + q.frames_b - 1, path_entries);
     if (!with_store) continue;
-    const long long bytes = 4 * dtw_bp_words(q.frames_a, q.frames_b);
-    if (q.scratch_off < 0)
-      TTS_CHECK_ARG(bytes <= lds_bp_bytes, "%s: pair %d: %lld bytes of back-pointers do not fit the %d bytes of LDS asked for", what, p, bytes,
-                    lds_bp_bytes);
-    else
-      TTS_CHECK_ARG(q.scratch_off % 4 == 0 && q.scratch_off + bytes <= scratch_bytes,
-                    "%s: pair %d: %lld bytes of back-pointers at %lld do not fit the scratch buffer (%lld bytes)", what, p, bytes,
-                    (long long)q.scratch_off, scratch_bytes);
+    if (int rc = check_bp_slot(what, p, 4 * bp_words(q.frames_a, q.frames_b), q.scratch_off, lds_bp_bytes, scratch_bytes)) return rc;
   }
   const hipError_t e = hipMemcpyAsync(dev, host, (size_t)n_pairs * sizeof(TtsDtwPair), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) {

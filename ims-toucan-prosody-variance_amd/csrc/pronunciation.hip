@@ -8,6 +8,7 @@
 // Batch independence: one workgroup per utterance, every sum in an order that depends on the utterance alone, no atomics and no
 // workgroup waits on another one.
 #include "common.h"
+#include "pair_sweep.h"
 #include "../../include/toucan_pronunciation.h"
 
 namespace tts {
@@ -368,14 +369,26 @@ __global__ __launch_bounds__(P_THREADS) void ctc_beam_kernel(const float* __rest
 }
 
 // ---- edit distance, one workgroup per pair --------------------------------------------------------------------------------------
-// tts_dtw's sweep on integers: the reference tokens in bands of 256, thread t owning row i = band + t + 1; at step s of the band's
-// anti-diagonal sweep it forms the cell (i, s - t + 1).  D of the last two anti-diagonals lies in diag[2][256]: D(i-1, j) is what
-// thread t - 1 wrote a step ago, D(i-1, j-1) is what this thread read there a step ago and kept, D(i, j-1) its own last value.  Thread
-// 0 takes both from row[], D of the band before's last row (or D(0, j) = j), which thread 255 overwrites 255 columns behind thread 0's
-// reads.  Back-pointers of the cells i, j >= 1: 2 bits (0 diagonal, 1 deletion, 2 insertion), 16 per word.  Thread 0 walks back and
-// writes both maps as it goes: every token is met exactly once.
+// The sweep of pair_sweep.h over integer costs, rows (reference tokens) and columns (decoded tokens) counted from 1: D(i, 0) = i,
+// D(0, j) = j, a thread keeps its reference token and a cell takes the diagonal plus a mismatch, a deletion (up) plus 1 or an
+// insertion (left) plus 1.  Thread 0 walks back and writes both maps as it goes: every token is met exactly once.
 constexpr int E_MAX_HYP = TTS_EDIT_MAX_HYP;
+static_assert(P_THREADS == SWEEP_THREADS, "the sweep's workgroup");
 static_assert(4 * (E_MAX_HYP + 1) + 4 * E_MAX_HYP + 8 * P_THREADS + TTS_EDIT_LDS_BP_BYTES + 64 <= 64 * 1024, "LDS budget without a raised limit");
+
+struct EditCells {
+  using value_t = int;
+  static constexpr int ORIGIN = 1;
+  const int *ref, *hyp;
+  int mine;
+
+  __device__ __forceinline__ void band(int i, bool active) { mine = active ? ref[i - 1] : 0; }
+  __device__ __forceinline__ int border(int i, int j) const { return j == 0 ? i : j; }  // D(i, 0) = i, D(0, j) = j
+  __device__ __forceinline__ void step(int, bool) const {}
+  __device__ __forceinline__ int via(unsigned int code, int pred, int j) const { return pred + (code || mine != hyp[j - 1] ? 1 : 0); }
+  __device__ __forceinline__ int cell(int, int, int best) const { return best; }
+  __device__ __forceinline__ void last(int) const {}
+};
 
 __global__ __launch_bounds__(P_THREADS) void edit_distance_kernel(const int* __restrict__ ref_ids, const int* __restrict__ hyp_id,
                                                                   const int* __restrict__ n_hyp, const TtsPronUtt* __restrict__ utts,
@@ -394,57 +407,16 @@ __global__ __launch_bounds__(P_THREADS) void edit_distance_kernel(const int* __r
   }
   const int* ref = ref_ids + u.ref_begin;
   const int Wd = (H + 15) >> 4;
-  const bool in_lds = u.scratch_off < 0;
-  unsigned int* bp = in_lds ? reinterpret_cast<unsigned int*>(e_lds) : reinterpret_cast<unsigned int*>(scratch + u.scratch_off);
   for (int j = tid; j < H; j += P_THREADS) hyp_s[j] = hyp_id[(size_t)u.frame_begin + j];
   __syncthreads();
-  if (H > 0) {
-    for (int i0 = 0; i0 < R; i0 += P_THREADS) {
-      const int i = i0 + tid + 1;
-      const bool active = i <= R;
-      const bool feeds_next = tid == P_THREADS - 1 && i0 + P_THREADS < R;
-      const int steps = min(P_THREADS, R - i0) + H - 1;
-      const int mine = active ? ref[i - 1] : 0;
-      int left = i, kept_up = i - 1;  // D(i, 0), D(i - 1, 0)
-      unsigned int word = 0;
-      unsigned int* bp_row = bp + (size_t)(i - 1) * Wd;
-      for (int s = 0; s < steps; ++s) {
-        const int j = s - tid + 1;
-        if (active && j >= 1 && j <= H) {
-          const int up = tid == 0 ? (i0 == 0 ? j : row[j]) : diag[((s - 1) & 1) * P_THREADS + tid - 1];
-          int best = kept_up + (mine != hyp_s[j - 1] ? 1 : 0);
-          unsigned int code = 0;
-          if (up + 1 < best) {
-            best = up + 1;
-            code = 1;
-          }
-          if (left + 1 < best) {
-            best = left + 1;
-            code = 2;
-          }
-          kept_up = up;
-          left = best;
-          diag[(s & 1) * P_THREADS + tid] = best;
-          if (feeds_next) row[j] = best;
-          const int jj = j - 1;
-          word |= code << (2 * (jj & 15));
-          if ((jj & 15) == 15 || j == H) {
-            bp_row[jj >> 4] = word;
-            word = 0;
-          }
-        }
-        __syncthreads();
-      }
-    }
-  }
-  if (!in_lds) __threadfence_block();
-  __syncthreads();
+  EditCells cells = {ref, hyp_s, 0};
+  const unsigned int* bp = pair_sweep(cells, R, H, row, diag, u.scratch_off, e_lds, scratch);
   if (tid == 0) {
     int* r2h = ref_to_hyp + u.ref_begin;
     int* h2r = hyp_to_ref + u.frame_begin;
     int i = R, j = H, hits = 0, subs = 0, dels = 0, ins = 0;
     while (i > 0 || j > 0) {
-      const unsigned int code = i == 0 ? 2u : j == 0 ? 1u : (bp[(size_t)(i - 1) * Wd + ((j - 1) >> 4)] >> (2 * ((j - 1) & 15))) & 3u;
+      const unsigned int code = i == 0 ? 2u : j == 0 ? 1u : bp_code<EditCells::ORIGIN>(bp, Wd, i, j);
       if (code == 0) {
         if (ref[i - 1] == hyp_s[j - 1]) ++hits;
         else ++subs;
@@ -628,14 +600,7 @@ int edit_distance(const int* ref_ids, int n_ref_total, const int* hyp_id, int ro
   for (int b = 0; b < n; ++b) {
     const TtsPronUtt& q = host[b];
     const long long cap = q.n_frames < E_MAX_HYP ? q.n_frames : E_MAX_HYP;
-    const long long bytes = 4ll * q.n_ref * ((cap + 15) / 16);
-    if (q.scratch_off < 0)
-      TTS_CHECK_ARG(bytes <= lds_bp_bytes, "edit_distance: pair %d: %lld bytes of back-pointers do not fit the %d bytes of LDS asked for", b, bytes,
-                    lds_bp_bytes);
-    else
-      TTS_CHECK_ARG(q.scratch_off % 4 == 0 && q.scratch_off + bytes <= scratch_bytes,
-                    "edit_distance: pair %d: %lld bytes of back-pointers at %lld do not fit the scratch buffer (%lld bytes)", b, bytes,
-                    (long long)q.scratch_off, scratch_bytes);
+    if (int rc = check_bp_slot("edit_distance", b, 4 * bp_words(q.n_ref, (int)cap), q.scratch_off, lds_bp_bytes, scratch_bytes)) return rc;
   }
   const int rc = upload_utts("edit_distance", host, dev, n, rows, n_ref_total, TTS_EDIT_MAX_REF, st);
   if (rc != TTS_OK) return rc;

@@ -7,23 +7,17 @@
 #include <math.h>
 
 #include "common.h"
+#include "ctc_lattice.h"
 #include "../../include/toucan_score.h"
 
 namespace tts {
 
-// ---- CTC: forward variables over the extended label sequence, fp64, one workgroup per utterance -------------------------------
+// ---- CTC: the forward variables of ctc_lattice.h, one workgroup per utterance --------------------------------------------------
 // Frames are taken in chunks of CTC_CHUNK: first the four wavefronts compute the log-softmax of the chunk's rows side by side (no
 // dependency between frames) into LDS, then the workgroup walks the chunk's frames one after the other, one barrier per frame.
-// LDS: alpha [2][S] fp64 (double-buffered rows), the extended labels [S] int32 (bit 31: the skip transition s-2 -> s is allowed),
-// the chunk's log-probabilities [CTC_CHUNK][n_symbols] fp32.
-constexpr int CTC_THREADS = 256, CTC_CHUNK = 32, CTC_MAX_SYMBOLS = 256;
-
-// log(exp(a) + exp(b) + exp(c)) in fp64; -inf when all three are -inf
-__device__ inline double lse3(double a, double b, double c) {
-  const double m = fmax(a, fmax(b, c));
-  if (m == -INFINITY) return -INFINITY;
-  return m + log(exp(a - m) + exp(b - m) + exp(c - m));
-}
+// LDS: alpha [2][S] fp64 (double-buffered rows), the extended labels [S] int32, the chunk's log-probabilities
+// [CTC_CHUNK][n_symbols] fp32.
+constexpr int CTC_CHUNK = 32, CTC_MAX_SYMBOLS = 256;
 
 __global__ __launch_bounds__(CTC_THREADS) void ctc_loss_kernel(const float* __restrict__ logits, int ld, int n_sym,
                                                                const int* __restrict__ frame_begin, const int* __restrict__ n_frames,
@@ -42,21 +36,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_loss_kernel(const float* __re
     if (tid == 0) loss[b] = NAN;
     return;
   }
-  // extended labels: blank, l1, blank, l2, ..., blank; the skip is allowed into a label that differs from the label two states back
   __shared__ int bad;
-  if (tid == 0) bad = 0;
-  __syncthreads();
-  for (int s = tid; s < S; s += CTC_THREADS) {
-    int v = blank;
-    if (s & 1) {
-      v = tg[s >> 1];
-      if (v < 0 || v >= n_sym || v == blank) bad = 1;  // (benign race: every writer stores 1)
-      else if (s >= 3 && tg[(s >> 1) - 1] != v) v |= INT32_MIN;
-    }
-    lab[s] = v;
-  }
-  __syncthreads();
-  if (bad) {  // a target id outside the symbols, or the blank itself: no defined loss
+  if (ctc_extended_labels(lab, tg, n, n_sym, blank, &bad)) {
     if (tid == 0) loss[b] = NAN;
     return;
   }
@@ -64,30 +45,14 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_loss_kernel(const float* __re
   double* cur = alpha + s_pad;
   for (int c0 = 0; c0 < T; c0 += CTC_CHUNK) {
     const int nc = min(CTC_CHUNK, T - c0);
-    // log_softmax of the chunk's frames, as the reference's fp32 log_softmax forms it: (x - max) - log(sum exp(x - max))
-    for (int f = wv; f < nc; f += CTC_THREADS / 64) {
-      const float* xr = x0 + (size_t)(c0 + f) * ld;
-      float m = -INFINITY;
-      for (int k = lane; k < n_sym; k += 64) m = fmaxf(m, xr[k]);
-      m = wave_max(m);
-      float s = 0.0f;
-      for (int k = lane; k < n_sym; k += 64) s += expf(xr[k] - m);
-      const float ls = logf(wave_sum(s));
-      for (int k = lane; k < n_sym; k += 64) lp[f * n_sym + k] = (xr[k] - m) - ls;
-    }
+    for (int f = wv; f < nc; f += CTC_THREADS / 64) ctc_log_softmax_row(x0 + (size_t)(c0 + f) * ld, n_sym, lane, lp + f * n_sym);
     __syncthreads();
     for (int f = 0; f < nc; ++f) {
       const float* lpf = lp + f * n_sym;
-      if (c0 + f == 0) {  // alpha_0: start in the first blank or in the first label
-        for (int s = tid; s < S; s += CTC_THREADS) cur[s] = s < 2 ? (double)lpf[lab[s] & 0x7fffffff] : -INFINITY;
+      if (c0 + f == 0) {
+        for (int s = tid; s < S; s += CTC_THREADS) cur[s] = ctc_alpha_init(lab, s, lpf);
       } else {
-        for (int s = tid; s < S; s += CTC_THREADS) {
-          const int v = lab[s];
-          const double a = prev[s];
-          const double bb = s >= 1 ? prev[s - 1] : -INFINITY;
-          const double cc = v < 0 ? prev[s - 2] : -INFINITY;
-          cur[s] = lse3(a, bb, cc) + (double)lpf[v & 0x7fffffff];
-        }
+        for (int s = tid; s < S; s += CTC_THREADS) cur[s] = ctc_alpha_step(prev, lab, s, lpf);
       }
       __syncthreads();
       double* t = prev;
@@ -96,8 +61,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_loss_kernel(const float* __re
     }
   }
   if (tid == 0) {
-    const double ll = S >= 2 ? lse3(prev[S - 1], prev[S - 2], -INFINITY) : prev[S - 1];
-    const double nll = -ll;
+    const double nll = -ctc_log_likelihood(prev, S);
     loss[b] = isinf(nll) ? 0.0f : (float)(nll / (double)max(n, 1));  // zero_infinity; reduction "mean" at batch 1
   }
 }
@@ -126,8 +90,6 @@ int ctc_loss(const float* logits, int ld, int n_sym, const int* frame_begin, con
 // Each thread accumulates a fixed, strided subset of the utterance's elements in fp64; the 256 partial sums are added by a
 // fixed-order tree.  The element differences are fp32, as in the reference (L1Loss / MSELoss on fp32 tensors).
 constexpr int LOSS_THREADS = 256;
-
-__device__ inline float log_rn(float x) { return (float)log((double)x); }  // correctly rounded fp32 log
 
 __global__ __launch_bounds__(LOSS_THREADS) void score_losses_kernel(const float* __restrict__ before, int ld_b, const float* __restrict__ after,
                                                                     int ld_a, const float* __restrict__ gold, int ld_g,

@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "ctc_lattice.h"
 #include "../../include/toucan_train.h"
 
 namespace tts {
@@ -321,18 +322,12 @@ int lstm_backward_step(const float* dy, int lddy, const float* w_hh, const float
 }
 
 // ---- CTC loss and its gradient with respect to the logits, one workgroup -----------------------------------------------------------
-// Pass 1: the fp32 log-softmax of every frame into lp (the four wavefronts side by side).  Pass 2: the forward variables alpha over
-// the S = 2n+1 extended states, fp64, two rows in LDS and every row to global scratch.  Pass 3, frames backwards: the backward
+// The lattice of ctc_lattice.h.  Pass 1: the log-softmax of every frame into lp (the four wavefronts side by side).  Pass 2: the
+// forward variables alpha, two rows in LDS and every row to global scratch.  Pass 3, frames backwards: the backward
 // variables beta (two rows in LDS); per state the posterior exp(alpha + beta - lp - ll) into LDS; then one thread per symbol adds
 // the posteriors of the symbol's states along a list (first[k], next[s]: ascending s, a fixed order) and writes
 // grad = (softmax - posterior) / n.  The state loops run in strides of the workgroup, so S may exceed 256.
-constexpr int CG_THREADS = 256, CG_MAX_SYMBOLS = 256;
-
-__device__ inline double lse3d(double a, double b, double c) {
-  const double m = fmax(a, fmax(b, c));
-  if (m == -INFINITY) return -INFINITY;
-  return m + log(exp(a - m) + exp(b - m) + exp(c - m));
-}
+constexpr int CG_THREADS = CTC_THREADS, CG_MAX_SYMBOLS = 256;
 
 __global__ __launch_bounds__(CG_THREADS) void ctc_grad_kernel(const float* __restrict__ logits, int ld, int n_sym, int T,
                                                               const int* __restrict__ targets, int n, int blank, double* __restrict__ alpha,
@@ -347,19 +342,7 @@ __global__ __launch_bounds__(CG_THREADS) void ctc_grad_kernel(const float* __res
   __shared__ int bad;
   __shared__ double ll_s;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, S = 2 * n + 1;
-  if (tid == 0) bad = 0;
-  __syncthreads();
-  for (int s = tid; s < S; s += CG_THREADS) {
-    int v = blank;
-    if (s & 1) {
-      v = targets[s >> 1];
-      if (v < 0 || v >= n_sym || v == blank) bad = 1;  // (benign race: every writer stores 1)
-      else if (s >= 3 && targets[(s >> 1) - 1] != v) v |= INT32_MIN;
-    }
-    lab[s] = v;
-  }
-  __syncthreads();
-  if (bad) {  // no defined loss: report, as tts_ctc_loss does
+  if (ctc_extended_labels(lab, targets, n, n_sym, blank, &bad)) {  // no defined loss: report, as tts_ctc_loss does
     if (tid == 0) loss[0] = NAN;
     for (int i = tid; i < T * n_sym; i += CG_THREADS) grad[(size_t)(i / n_sym) * ldg + i % n_sym] = NAN;
     return;
@@ -376,17 +359,8 @@ __global__ __launch_bounds__(CG_THREADS) void ctc_grad_kernel(const float* __res
     }
     if (prev >= 0) next[prev] = -1;
   }
-  // pass 1: log_softmax as the reference's fp32 one forms it: (x - max) - log(sum exp(x - max))
-  for (int t = wv; t < T; t += CG_THREADS / 64) {
-    const float* xr = logits + (size_t)t * ld;
-    float m = -INFINITY;
-    for (int k = lane; k < n_sym; k += 64) m = fmaxf(m, xr[k]);
-    m = wave_max(m);
-    float s = 0.0f;
-    for (int k = lane; k < n_sym; k += 64) s += expf(xr[k] - m);
-    const float ls = logf(wave_sum(s));
-    for (int k = lane; k < n_sym; k += 64) lp[(size_t)t * n_sym + k] = (xr[k] - m) - ls;
-  }
+  // pass 1
+  for (int t = wv; t < T; t += CG_THREADS / 64) ctc_log_softmax_row(logits + (size_t)t * ld, n_sym, lane, lp + (size_t)t * n_sym);
   __syncthreads();  // lp is read below by other threads of this workgroup than wrote it
   // pass 2: alpha
   double* prev = rows;
@@ -394,15 +368,7 @@ __global__ __launch_bounds__(CG_THREADS) void ctc_grad_kernel(const float* __res
   for (int t = 0; t < T; ++t) {
     const float* lpt = lp + (size_t)t * n_sym;
     for (int s = tid; s < S; s += CG_THREADS) {
-      const int v = lab[s];
-      double a;
-      if (t == 0) {
-        a = s < 2 ? (double)lpt[v & 0x7fffffff] : -INFINITY;
-      } else {
-        const double bb = s >= 1 ? prev[s - 1] : -INFINITY;
-        const double cc = v < 0 ? prev[s - 2] : -INFINITY;
-        a = lse3d(prev[s], bb, cc) + (double)lpt[v & 0x7fffffff];
-      }
+      const double a = t == 0 ? ctc_alpha_init(lab, s, lpt) : ctc_alpha_step(prev, lab, s, lpt);
       cur[s] = a;
       alpha[(size_t)t * S + s] = a;
     }
@@ -411,7 +377,7 @@ __global__ __launch_bounds__(CG_THREADS) void ctc_grad_kernel(const float* __res
     prev = cur;
     cur = tmp;
   }
-  if (tid == 0) ll_s = S >= 2 ? lse3d(prev[S - 1], prev[S - 2], -INFINITY) : prev[S - 1];
+  if (tid == 0) ll_s = ctc_log_likelihood(prev, S);
   __syncthreads();
   const double ll = ll_s;
   const double inv_n = 1.0 / (double)n;
@@ -432,7 +398,7 @@ __global__ __launch_bounds__(CG_THREADS) void ctc_grad_kernel(const float* __res
       } else {
         const double bb = s + 1 < S ? prev[s + 1] : -INFINITY;
         const double cc = (s + 2 < S && lab[s + 2] < 0) ? prev[s + 2] : -INFINITY;
-        b = lse3d(prev[s], bb, cc) + l;
+        b = lse3(prev[s], bb, cc) + l;
       }
       cur[s] = b;
       post[s] = exp(alpha[(size_t)t * S + s] + b - l - ll);  // alpha and beta both hold this frame's lp; exp(-inf) = 0

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import align, capi
+from .ragged import begins, plan_bp_store
 
 SR = 16000
 BLANK = 144  # Aligner.py:60: CTCLoss(blank=144, zero_infinity=True)
@@ -103,10 +104,6 @@ def summarise(counts, n_ref, posteriors):
     return out
 
 
-def _begins(counts):
-    return [int(b) for b in np.concatenate([[0], np.cumsum(counts)[:-1]])] if len(counts) else []
-
-
 class PronunciationChecker:
     """``check(texts, waves, sr)``: one dict per utterance (below); ``recognise`` decodes only; ``check_logits`` starts from given
     posteriors; ``best_path``, ``beam_search``, ``edit_distance`` and ``phone_posteriors`` are the four kernels on their own."""
@@ -131,7 +128,7 @@ class PronunciationChecker:
     def _table(self, rag, ref_counts=None, scratch_off=None):
         B = rag.n_seq
         table = (capi.TtsPronUtt * max(B, 1))()
-        rb = _begins(ref_counts) if ref_counts is not None else [0] * B
+        rb = begins(ref_counts) if ref_counts is not None else [0] * B
         for b in range(B):
             table[b] = capi.TtsPronUtt(int(rag.begins[b]), int(rag.lengths[b]), rb[b], 0 if ref_counts is None else int(ref_counts[b]),
                                        -1 if scratch_off is None else int(scratch_off[b]))
@@ -170,7 +167,7 @@ class PronunciationChecker:
             raise ValueError("the beam search needs a beam of at least 1")
         ops, rows, B = self.ops, int(logits.shape[0]), rag.n_seq
         words = [2 * n * beam for n in rag.lengths]
-        table, dev = self._table(rag, scratch_off=_begins(words))
+        table, dev = self._table(rag, scratch_off=begins(words))
         scratch = torch.empty(max(sum(words), 1), dtype=torch.int32, device=self.device)
         out = {"hyp_id": torch.zeros(max(rows, 1), dtype=torch.int32, device=self.device),
                "n_hyp": torch.zeros(max(B, 1), dtype=torch.int32, device=self.device),
@@ -194,15 +191,7 @@ class PronunciationChecker:
         for b, n in enumerate(n_ref):
             if n > MAX_REF:
                 raise ValueError(f"utterance {b}: {n} reference tokens; the edit distance takes at most {MAX_REF}")
-        off, total, lds = [], 0, 0
-        for n, T in zip(n_ref, rag.lengths):
-            need = bp_bytes(n, T)
-            if force_scratch or need > LDS_BP_BYTES:
-                off.append(total)
-                total += need
-            else:
-                off.append(-1)
-                lds = max(lds, need)
+        off, total, lds = plan_bp_store([bp_bytes(n, T) for n, T in zip(n_ref, rag.lengths)], LDS_BP_BYTES, force_scratch)
         table, dev = self._table(rag, ref_counts=n_ref, scratch_off=off)
         scratch = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
         ids = self._i32(np.concatenate([np.asarray(r, dtype=np.int32).reshape(-1) for r in refs] + [np.zeros(1, dtype=np.int32)]))
@@ -210,7 +199,7 @@ class PronunciationChecker:
         r2h = torch.full((max(sum(n_ref), 1),), int(fill), dtype=torch.int32, device=self.device)
         h2r = torch.full((max(rows, 1),), int(fill), dtype=torch.int32, device=self.device)
         capi.check(ops.lib.tts_edit_distance(ids.data_ptr(), int(sum(n_ref)), hyp_id.data_ptr(), rows, n_hyp.data_ptr(), table, dev.data_ptr(), B,
-                                             scratch.data_ptr(), total, (lds + 15) // 16 * 16, counts.data_ptr(), r2h.data_ptr(), h2r.data_ptr(),
+                                             scratch.data_ptr(), total, lds, counts.data_ptr(), r2h.data_ptr(), h2r.data_ptr(),
                                              ops.stream()), "tts_edit_distance")
         return counts[:B], r2h[:sum(n_ref)], h2r
 
@@ -298,7 +287,7 @@ class PronunciationChecker:
         post = self.phone_posteriors(logits, rag, dur, [t[2] for t in toks])
         results = self._hypotheses(dec, rag, beam)
         counts, r2h, h2r, loss, post, dur = (t.cpu().numpy() for t in (counts, r2h, h2r, loss, post, dur))
-        rb = _begins([len(t[3]) for t in toks])
+        rb = begins([len(t[3]) for t in toks])
         for b, (r, t) in enumerate(zip(results, toks)):
             L, ref_tokens, n_ref = len(t[1]), t[4], len(t[3])
             rows = post[full_begin[b]:full_begin[b] + L]

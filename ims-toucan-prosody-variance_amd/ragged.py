@@ -10,6 +10,26 @@ import numpy as np
 import torch
 
 
+def begins(counts):
+    """Where each of consecutive runs of ``counts`` items begins."""
+    return [int(b) for b in np.concatenate([[0], np.cumsum(counts)[:-1]])] if len(counts) else []
+
+
+def plan_bp_store(needs, lds_limit, force_scratch=False):
+    """Where every pair of one launch keeps its back-pointers (csrc/pair_sweep.h).  needs: the bytes of each pair; a pair of more
+    than lds_limit bytes (with force_scratch: every pair) keeps them in the scratch buffer.  -> (per pair its offset into the
+    scratch buffer, -1 for LDS; the scratch bytes; the LDS bytes to ask for, rounded up to 16)."""
+    off, total, lds = [], 0, 0
+    for need in needs:
+        if force_scratch or need > lds_limit:
+            off.append(total)
+            total += need
+        else:
+            off.append(-1)
+            lds = max(lds, need)
+    return off, total, (lds + 15) // 16 * 16
+
+
 class Ragged:
     _cache = {}
 

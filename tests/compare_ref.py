@@ -8,7 +8,8 @@ import numpy as np
 
 N_MELS, N_CEP = 80, 13
 SUM_COLUMNS = ("mcd", "diag", "vv", "sq_hz", "sq_cents", "x", "y", "xx", "yy", "xy", "gross", "vuv")
-CASE_SIZES = ((1, 1), (1, 7), (5, 3), (64, 64), (65, 130), (257, 190), (300, 420), (4096, 64))
+CASE_SIZES = ((1, 1), (1, 7), (5, 3), (64, 64), (65, 130), (257, 190), (300, 420), (4096, 64),
+              (2, 15), (3, 17), (256, 16), (513, 33))  # widths on either side of a back-pointer word; one band exactly, just past two
 MIN_GAP = 1e-10  # every decision of every case is wider than this (relative): eight orders above fp64 rounding
 
 

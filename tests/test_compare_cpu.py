@@ -177,11 +177,11 @@ def test_back_pointer_bytes_and_launch_plan():
     sizes = [compare.bp_bytes(ta, tb) for ta, tb in cr.CASE_SIZES]
     assert min(sizes) <= compare.LDS_BP_BYTES < max(sizes)  # the cases lie on both sides of the LDS form's limit
     fa, fb = [ta for ta, _ in cr.CASE_SIZES], [tb for _, tb in cr.CASE_SIZES]
-    assert compare.plan_launches(fa, fb) == [(0, 8)] and compare.plan_launches([], []) == []
-    assert compare.plan_launches(fa, fb, max_scratch_bytes=1) == [(0, 8)]  # only the largest uses the scratch buffer
-    assert compare.plan_launches(fa, fb, force_scratch=True, max_scratch_bytes=sizes[5] + sizes[6]) == [(0, 6), (6, 7), (7, 8)]
+    assert compare.plan_launches(fa, fb) == [(0, 12)] and compare.plan_launches([], []) == []
+    assert compare.plan_launches(fa, fb, max_scratch_bytes=1) == [(0, 8), (8, 12)]  # only the largest, pair 7, uses the scratch buffer
+    assert compare.plan_launches(fa, fb, force_scratch=True, max_scratch_bytes=sizes[5] + sizes[6]) == [(0, 6), (6, 7), (7, 8), (8, 12)]
     plans = compare.plan_launches(fa, fb, force_scratch=True, max_scratch_bytes=1)
-    assert plans == [(p, p + 1) for p in range(8)]  # a pair larger than the bound still gets its launch
+    assert plans == [(p, p + 1) for p in range(12)]  # a pair larger than the bound still gets its launch
     many = compare.plan_launches([4096] * 600, [4096] * 600)
     assert many == [(0, 256), (256, 512), (512, 600)]
 

@@ -39,7 +39,7 @@ def same(x, y):
 # ---- tts_dtw ------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def batch_runs(cmp):
-    """All eight cases in one ragged batch, once per form of the back-pointer store: {force_scratch: (costs, paths)}."""
+    """All the cases in one ragged batch, once per form of the back-pointer store: {force_scratch: (costs, paths)}."""
     return {force: cmp.dtw(*packed(range(N)), force_scratch=force) for force in (False, True)}
 
 

@@ -98,6 +98,29 @@ def test_ctc_batch_equals_one_by_one_bit_for_bit(ops):
     assert (batch[::7] == 0).all()
 
 
+@pytest.mark.parametrize("T, n", [(33, 4), (140, 130)])
+def test_ctc_loss_and_ctc_grad_return_the_same_loss(ops, T, n):
+    """tts_ctc_loss at batch 1 and tts_ctc_grad walk one lattice (csrc/ctc_lattice.h) and reach the same fp64 log-likelihood by the
+    same operations; then one divides nll / n and the other multiplies nll * (1 / n), at most one fp64 ulp apart, which is at most
+    one float32 step after the rounding.  T = 33 crosses the loss kernel's chunk of 32 frames; T = 140 with n = 130 has S = 261
+    states, past one stride of 256, and ends in a chunk of 12."""
+    rng = np.random.default_rng(1000 * T + n)
+    lg = rng.normal(0.0, 3.0, size=(T, 145)).astype(np.float32)
+    ids = ((np.arange(n) * 7 + int(rng.integers(0, 144))) % 144).astype(np.int32)  # 7 is no divisor of 144: neighbours differ
+    assert (np.diff(ids) != 0).all() and ids.min() >= 0 and ids.max() < 144
+    x = torch.from_numpy(lg).to(ops.device)
+    a = float(scorer.ctc_loss_batch(ops, x, Ragged([T], ops.device), [ids]).cpu()[0])
+    alpha = torch.empty(T * (2 * n + 1), dtype=torch.float64, device=ops.device)
+    lp, loss, grad = (torch.zeros(s, dtype=torch.float32, device=ops.device) for s in ((T, 145), (1,), (T, 145)))
+    targets = torch.from_numpy(ids).to(ops.device)
+    capi.check(ops.lib.tts_ctc_grad(x.data_ptr(), 145, 145, T, targets.data_ptr(), n, 144, alpha.data_ptr(), lp.data_ptr(), loss.data_ptr(),
+                                    grad.data_ptr(), 145, ops.stream()), "tts_ctc_grad")
+    b = float(loss.cpu()[0])
+    print(f"T {T}, n {n}: tts_ctc_loss {a!r}, tts_ctc_grad {b!r}, one float32 step {float(np.spacing(np.float32(a)))!r}")
+    assert a == a and b == b and a != 0.0 and b != 0.0
+    assert abs(a - b) <= float(np.spacing(np.float32(max(abs(a), abs(b)))))
+
+
 def test_ctc_argument_checks(ops):
     lg = np.zeros((4, 145), dtype=np.float32)
     with pytest.raises(ValueError):
