@@ -340,6 +340,21 @@ FIDELITY_PROTOTYPES = {
 # include/toucan_fidelity.h TTS_FIDELITY_SUMS, _MAX_BINS, _MAX_BANDS, _MAX_HOP
 FIDELITY_SUMS, FIDELITY_MAX_BINS, FIDELITY_MAX_BANDS, FIDELITY_MAX_HOP = 4, 2049, 256, 4096
 
+# symbol -> (restype, argtypes); mirrors include/toucan_intelligibility.h (STOI and ESTOI of time-aligned pairs: csrc/intelligibility.hip) one to one
+INTELLIGIBILITY_PROTOTYPES = {
+    "tts_stoi_select_sweep": (C.c_int, []),
+    "tts_stoi_segments_per_group": (C.c_int, []),
+    "tts_stoi_frame_energy": (C.c_int, [_p, _l, _p, _p, _i, _p, _l, _p, _p]),
+    "tts_stoi_select": (C.c_int, [_p, _p, _p, _i, _l, _l, _p, _p, _p]),
+    "tts_stoi_gather": (C.c_int, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _p, _p, _l, _p, _p]),
+    "tts_stoi_bands": (C.c_int, [_p, _l, _l, _p, _p]),
+    "tts_stoi_segments": (C.c_int, [_p, _l, _p, _p, _p, _p, _i, _l, _p, _p]),
+    "tts_stoi_reduce": (C.c_int, [_p, _p, _i, _l, _p, _p]),
+}
+# include/toucan_intelligibility.h TTS_STOI_RATE, _FRAME, _HOP, _BINS, _BANDS, _SEGMENT, _MAX_FRAMES, _BAND_EDGES
+STOI_RATE, STOI_FRAME, STOI_HOP, STOI_BINS, STOI_BANDS, STOI_SEGMENT, STOI_MAX_FRAMES = 10000, 256, 128, 257, 15, 30, 8388608
+STOI_BAND_EDGES = (7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219)
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -366,7 +381,8 @@ def lib():
             list(GAN_PROTOTYPES.items()) + list(PITCH_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()) + \
             list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()) + \
             list(PRONUNCIATION_PROTOTYPES.items()) + list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()) + \
-            list(TRUEPEAK_PROTOTYPES.items()) + list(FIDELITY_PROTOTYPES.items()) + list(FIT_PROTOTYPES.items()):
+            list(TRUEPEAK_PROTOTYPES.items()) + list(FIDELITY_PROTOTYPES.items()) + list(FIT_PROTOTYPES.items()) + \
+            list(INTELLIGIBILITY_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

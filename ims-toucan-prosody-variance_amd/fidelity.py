@@ -251,6 +251,7 @@ class CopySynthesis:
         self.device, self.ops = self.measure.device, self.measure.ops
         self.logmel = style.LogMel(self.device)
         self.vocode = vocode
+        self._intelligibility = None  # intelligibility.Intelligibility, built on first use
 
     @torch.inference_mode()
     def recordings_24k(self, waves, sr):
@@ -279,9 +280,21 @@ class CopySynthesis:
         return align.batched_log_mel(self.ops, self.logmel, spec, rag_rows), rag
 
     @torch.inference_mode()
-    def run(self, waves, sr, resolutions=DEFAULT_RESOLUTIONS, keep_frames=False, keep_waves=False):
+    def intelligibility_of(self, both, pair_spans):
+        """both: the packed 24 kHz wave; pair_spans: [(first sample of the generated signal, of the recording, samples)] -> the
+        records of ``intelligibility.Intelligibility.score_packed`` on the two at 10 kHz."""
+        if self._intelligibility is None:
+            from . import intelligibility
+            self._intelligibility = intelligibility.Intelligibility(self.device)
+        spans = [s for ga, rb, n in pair_spans for s in ((rb, n), (ga, n))]
+        wave10, spans10 = self.measure.resampler.resample(both, spans, SR, capi.STOI_RATE)
+        return self._intelligibility.score_packed(wave10, [(spans10[2 * p][0], spans10[2 * p + 1][0], spans10[2 * p][1]) for p in range(len(pair_spans))])
+
+    @torch.inference_mode()
+    def run(self, waves, sr, resolutions=DEFAULT_RESOLUTIONS, keep_frames=False, keep_waves=False, intelligibility=False):
         """-> one record of ``SpectralDistance.distance`` per recording; keep_waves adds ``generated`` and ``recording``, the two
-        24 kHz signals that were compared (device tensors)."""
+        24 kHz signals that were compared (device tensors); intelligibility adds ``stoi``, ``estoi`` and ``intelligibility_status``
+        of the same two signals at 10 kHz (intelligibility.py)."""
         if len(waves) == 0:
             return []
         packed24, spans24, frames = self.recordings_24k(waves, sr)
@@ -292,6 +305,9 @@ class CopySynthesis:
         both = torch.cat([wav, packed24])
         pair_spans = [(ga, at + rb, n) for ga, (rb, n) in zip(rag_w.begins, spans24)]
         records = self.measure.distance_packed(both, pair_spans, resolutions, keep_frames)
+        if intelligibility:
+            for rec, got in zip(records, self.intelligibility_of(both, pair_spans)):
+                rec.update(stoi=got["stoi"], estoi=got["estoi"], intelligibility_status=got["status"])
         if keep_waves:
             for rec, (ga, rb, n) in zip(records, pair_spans):
                 rec["generated"], rec["recording"] = both[ga: ga + n], both[rb: rb + n]
@@ -388,20 +404,25 @@ class VocoderScorer(ScoreBook):
         self.device = self.vocoder.device
         self.chain = CopySynthesis(self.vocoder.forward, self.device)
 
-    def score_waves(self, waves, sr, batch_size=32, keep_frames=False):
-        """waves: 1-D arrays or tensors at sr -> the records in the waves' order, batches of batch_size sorted by length."""
+    def score_waves(self, waves, sr, batch_size=32, keep_frames=False, intelligibility=False):
+        """waves: 1-D arrays or tensors at sr -> the records in the waves' order, batches of batch_size sorted by length;
+        intelligibility: every record also holds ``stoi``, ``estoi`` and ``intelligibility_status``."""
         from . import scorer
         records = [None] * len(waves)
         for batch in scorer._batches([int(np.shape(w)[0]) for w in waves], batch_size):
-            for i, rec in zip(batch, self.chain.run([waves[i] for i in batch], sr, keep_frames=keep_frames)):
+            for i, rec in zip(batch, self.chain.run([waves[i] for i in batch], sr, keep_frames=keep_frames, intelligibility=intelligibility)):
                 records[i] = rec
         return records
 
-    def score(self, paths_or_waves, sr=None, batch_size=32):
+    def score(self, paths_or_waves, sr=None, batch_size=32, intelligibility=False, rank_by="mel_l1"):
         """
         call this to update the path_to_score dict with scores for these recordings: paths of audio files, or waveforms at ``sr``
-        (their keys are "wave <index>")
+        (their keys are "wave <index>"); intelligibility adds STOI and ESTOI to the records, and rank_by="estoi" (which implies it)
+        makes 1 - estoi the score the listing and the removal go by
         """
+        if rank_by not in ("mel_l1", "estoi"):
+            raise ValueError(f"rank_by is 'mel_l1' or 'estoi', not {rank_by!r}")
+        intelligibility = bool(intelligibility) or rank_by == "estoi"
         keys, waves, rates = [], [], []
         for index, item in enumerate(paths_or_waves):
             if isinstance(item, (str, os.PathLike)):
@@ -417,6 +438,6 @@ class VocoderScorer(ScoreBook):
         records = [None] * len(waves)
         for rate in sorted(set(rates)):  # one batch holds one rate
             idx = [i for i, r in enumerate(rates) if r == rate]
-            for i, rec in zip(idx, self.score_waves([waves[i] for i in idx], rate, batch_size)):
+            for i, rec in zip(idx, self.score_waves([waves[i] for i in idx], rate, batch_size, intelligibility=intelligibility)):
                 records[i] = rec
-        self.record_scores(keys, [r["mel_l1"] for r in records], records)
+        self.record_scores(keys, [1.0 - r["estoi"] if rank_by == "estoi" else r["mel_l1"] for r in records], records)

@@ -575,7 +575,7 @@ class ToucanTTSInterface(torch.nn.Module):
                 r.update(synth=s, recording=w, recording_sr=sr)
         return results
 
-    def vocoder_fidelity(self, recordings, sr=None, keep_waves=False):
+    def vocoder_fidelity(self, recordings, sr=None, keep_waves=False, intelligibility=False):
         """Additive API: copy-synthesis of ``recordings`` through this interface's own vocoder, at the precision it runs at
         (fidelity.CopySynthesis): every recording goes to 24 kHz and is cut to whole mel frames, its 16 kHz /
         80-bin log-mel - what the acoustic model would hand the vocoder - is vocoded, and the result is compared with the cut
@@ -583,7 +583,9 @@ class ToucanTTSInterface(torch.nn.Module):
         resolution the spectral convergence and the log-magnitude L1.  recordings: paths (style.read_audio), (wave, sample rate)
         tuples, or waveforms at ``sr``; several channels are averaged.  -> one dict per recording
         (``fidelity.SpectralDistance.distance`` documents it); with ``keep_waves`` it also holds "generated" and "recording", the
-        two 24 kHz signals that were compared, on the device.  Everything from the first resampling on stays on the device."""
+        two 24 kHz signals that were compared, on the device; with ``intelligibility`` also ``stoi``, ``estoi`` and
+        ``intelligibility_status`` of the same two signals (intelligibility.py, DESIGN.md section 23: what the precision or the
+        faster vocoder costs in intelligibility).  Everything from the first resampling on stays on the device."""
         from . import fidelity, style
         if getattr(self, "_fidelity_obj", None) is None:
             vocode = self.mel2wav.vocode if self.pipe is not None else self.mel2wav.forward
@@ -603,7 +605,7 @@ class ToucanTTSInterface(torch.nn.Module):
         results = [None] * len(waves)
         for rate in sorted(set(rates)):  # one batch holds one rate
             idx = [i for i, x in enumerate(rates) if x == rate]
-            for i, rec in zip(idx, self._fidelity_obj.run([waves[i] for i in idx], rate, keep_waves=keep_waves)):
+            for i, rec in zip(idx, self._fidelity_obj.run([waves[i] for i in idx], rate, keep_waves=keep_waves, intelligibility=intelligibility)):
                 results[i] = rec
         return results
 
