@@ -6,7 +6,7 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libtoucan_hip.so")
-SOURCES = ["conv1d.hip", "conv1d_wide.hip", "resblock.hip", "rowops.hip", "attention_mfma.hip", "sequence_ops.hip", "capi.hip", "pipeline.hip", "style.hip", "wavenet.hip", "ffn.hip", "conformer_conv.hip", "align.hip", "score.hip", "gan.hip", "pitch.hip", "train.hip", "resample.hip", "glow_forward.hip", "prosody.hip","compare.hip", "pronunciation.hip", "loudness.hip", "truepeak.hip", "fidelity.hip", "intelligibility.hip", "activity.hip"]
+SOURCES = ["conv1d.hip", "conv1d_wide.hip", "resblock.hip", "rowops.hip", "attention_mfma.hip", "sequence_ops.hip", "capi.hip", "pipeline.hip", "style.hip", "wavenet.hip", "ffn.hip", "conformer_conv.hip", "align.hip", "score.hip", "gan.hip", "pitch.hip", "train.hip", "resample.hip", "glow_forward.hip", "prosody.hip","compare.hip", "pronunciation.hip", "loudness.hip", "truepeak.hip", "fidelity.hip", "intelligibility.hip", "prominence.hip", "activity.hip"]
 
 
 def _hipcc():
@@ -17,7 +17,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(PKG, "..", "include", h) for h in ("toucan_tts.h", "toucan_align.h", "toucan_score.h", "toucan_gan.h", "toucan_pitch.h", "toucan_train.h", "toucan_resample.h", "toucan_prosody.h", "toucan_prosody_curves.h", "toucan_prosody_fit.h", "toucan_compare.h", "toucan_pronunciation.h", "toucan_loudness.h", "toucan_truepeak.h", "toucan_activity.h", "toucan_fidelity.h", "toucan_intelligibility.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(PKG, "..", "include", h) for h in ("toucan_tts.h", "toucan_align.h", "toucan_score.h", "toucan_gan.h", "toucan_pitch.h", "toucan_train.h", "toucan_resample.h", "toucan_prosody.h", "toucan_prosody_curves.h", "toucan_prosody_fit.h", "toucan_compare.h", "toucan_pronunciation.h", "toucan_loudness.h", "toucan_truepeak.h", "toucan_activity.h", "toucan_fidelity.h", "toucan_intelligibility.h", "toucan_prominence.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

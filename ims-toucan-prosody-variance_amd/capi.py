@@ -355,6 +355,18 @@ INTELLIGIBILITY_PROTOTYPES = {
 STOI_RATE, STOI_FRAME, STOI_HOP, STOI_BINS, STOI_BANDS, STOI_SEGMENT, STOI_MAX_FRAMES = 10000, 256, 128, 257, 15, 30, 8388608
 STOI_BAND_EDGES = (7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219)
 
+# symbol -> (restype, argtypes); mirrors include/toucan_prominence.h (word prominence and boundary strength from the wavelet transform of prosodic tracks: csrc/prominence.hip) one to one
+_d = C.c_double
+PROMINENCE_PROTOTYPES = {
+    "tts_prominence_max_frames": (C.c_int, []),
+    "tts_prominence_channels": (C.c_int, [_p, _p, _l, _p, _p, _i, _p, _p, _l, _p, _p]),
+    "tts_prominence_cwt": (C.c_int, [_p, _l, _p, _p, _i, _p, _p, _p]),
+    "tts_prominence_units": (C.c_int, [_p, _l, _p, _p, _i, _p, _p, _l, _d, _d, _d, _i, _i, _p, _p, _p]),
+}
+# include/toucan_prominence.h TTS_PROMINENCE_MAX_FRAMES, _CHANNELS, _SCALES, _MAX_TAPS, _TABLE_LD, _COLUMNS, _UTT_COLUMNS, _TILE
+PROMINENCE_MAX_FRAMES, PROMINENCE_CHANNELS, PROMINENCE_SCALES, PROMINENCE_MAX_TAPS, PROMINENCE_TABLE_LD = 65536, 3, 6, 1025, 1026
+PROMINENCE_N_COLUMNS, PROMINENCE_UTT_COLUMNS, PROMINENCE_TILE = 8, 6, 256
+
 _LIB = None
 ABI_VERSION = 15  # include/toucan_tts.h TTS_ABI_VERSION: struct layouts and prototypes mirrored below
 
@@ -382,7 +394,7 @@ def lib():
             list(PROSODY_PROTOTYPES.items()) + list(CURVE_PROTOTYPES.items()) + list(COMPARE_PROTOTYPES.items()) + \
             list(PRONUNCIATION_PROTOTYPES.items()) + list(LOUDNESS_PROTOTYPES.items()) + list(ACTIVITY_PROTOTYPES.items()) + \
             list(TRUEPEAK_PROTOTYPES.items()) + list(FIDELITY_PROTOTYPES.items()) + list(FIT_PROTOTYPES.items()) + \
-            list(INTELLIGIBILITY_PROTOTYPES.items()):
+            list(INTELLIGIBILITY_PROTOTYPES.items()) + list(PROMINENCE_PROTOTYPES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

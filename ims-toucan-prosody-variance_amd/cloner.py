@@ -72,6 +72,32 @@ class UtteranceCloner:
                                           on_line_fine_tune=on_line_fine_tune and self.fine_tune_aligner,
                                           dropout_masks=None if dropout_masks is None else [dropout_masks])[0]
 
+    def word_prominence(self, transcript, path, speech_bounds=None, weights=(1.0, 1.0, 0.5), band=(1, 3)):
+        """Additive: which words the speaker of a recording stresses (prominence.ProminenceMeter.measure).  The
+        speech span of the normalised 16 kHz recording (``speech_bounds`` as ``extract_prosody`` takes it: None, a (start, end)
+        pair or "detect") goes through the pitch tracker and the frame energy, the aligner of this cloner and MAS lay the
+        transcript's phonemes onto its frames.  -> dict ``report`` (float64 [words, 8], columns ``prominence.COLUMNS``), ``words``
+        ((start, stop) phonemes of every word) and ``durations``; ``prominence.to_emphasis(feats, report)`` turns it into Spans that
+        give another voice the same emphasis without cloning every duration."""
+        from . import prominence, prosody
+        from .phonemes import phones_to_features
+        if getattr(self, "_prominence_obj", None) is None:
+            self._prominence_obj = prominence.ProminenceMeter(self.device, extractor=self.extractor)
+        wave, sr = style.read_audio(path)
+        norm = style.normalize_reference_audio(wave, sr)
+        if isinstance(speech_bounds, str):
+            if speech_bounds != align.DETECT:
+                raise ValueError(f"speech_bounds takes a (start, end) pair or {align.DETECT!r}, not {speech_bounds!r}")
+            speech_bounds = align.detect_speech_bounds(self.extractor, [norm])[0]
+        if speech_bounds is not None:
+            norm = norm[int(speech_bounds[0]):int(speech_bounds[1])]
+        feats = phones_to_features(transcript, handle_missing=False) if isinstance(transcript, str) else transcript
+        feats = feats.float().cpu().numpy() if torch.is_tensor(feats) else feats
+        meter = self._prominence_obj
+        report = meter.measure([norm], style.SR, [feats], weights=weights, band=band)[0]
+        phones = meter.last["phoneme_frames"][0]
+        return {"report": report, "words": prosody.word_spans(feats), "durations": phones[:, 1] - phones[:, 0]}
+
     def clone_utterance(self, path_to_reference_audio_for_intonation, path_to_reference_audio_for_voice, transcription_of_intonation_reference,
                         filename_of_result=None, lang="de", f0=None, speech_bounds=None, z_noise=None, evaluate=False):
         """UtteranceCloner.py:147-164: the voice of one recording speaking with the prosody of another.  evaluate (additive): also

@@ -652,6 +652,47 @@ class ToucanTTSInterface(torch.nn.Module):
                 r["synth"] = w
         return results
 
+    def _prominence(self):
+        if getattr(self, "_prominence_obj", None) is None:
+            from . import prominence
+            self._prominence_obj = prominence.ProminenceMeter(self.device)
+        return self._prominence_obj
+
+    def word_prominence(self, texts, input_is_phones=True, weights=(1.0, 1.0, 0.5), band=(1, 3), keep_waves=False, **synthesis_keywords):
+        """Additive API: synthesise ``texts`` as one batch (``synthesize_batch`` with ``synthesis_keywords``: prosody scales, curves,
+        gold prosody, ``z_noise``, ``utterance_embeddings``) and measure in the AUDIO which words came out prominent and how strong
+        the breaks between them are (prominence.ProminenceMeter.measure): the waveform goes through the pitch
+        tracker and the frame energy, the phonemes are laid onto its frames by the durations the synthesis used
+        (``self.last_durations``), and the wavelet transform of the three tracks is read at every word of
+        ``prosody.word_spans``.  -> one dict per text: ``report`` (float64 [words, 8], columns ``prominence.COLUMNS``), ``words``
+        (their (start, stop) phonemes) and ``durations`` (frames per phoneme); with ``keep_waves`` also "synth" (float32, 24 kHz).
+        ``prominence.to_emphasis(feats, report)`` turns a report into Spans for ``prosody_curves=``.  The numbers compare settings of
+        one sentence, or a recording with its clone; they are of this definition alone (parity with the authors' toolkit is
+        unpinned).  ValueError for ``distributed=True``, for ``sample_rate`` / ``pcm16`` (the meter takes the 24 kHz float
+        waveform), for ``loudness`` and ``speech_level`` (the wave is divided by its peak anyway), a weight that is negative or not
+        finite, a band outside 0 .. 5, and what ``measure`` refuses."""
+        if synthesis_keywords.get("distributed"):
+            raise ValueError("word_prominence is not available with distributed=True: the meter runs on one device")
+        if synthesis_keywords.get("sample_rate") is not None or synthesis_keywords.get("pcm16"):
+            raise ValueError("word_prominence measures the 24 kHz float waveform: sample_rate / pcm16 do not apply")
+        if synthesis_keywords.get("loudness") is not None:
+            raise ValueError("word_prominence divides the wave by its peak before it measures it: loudness does not apply")
+        if synthesis_keywords.get("speech_level") is not None:
+            raise ValueError("word_prominence divides the wave by its peak before it measures it: speech_level does not apply")
+        from . import prominence
+        prominence.check_weights(weights)
+        prominence.check_band(band)
+        feats = [t if torch.is_tensor(t) else self.text2phone.string_to_tensor(t, input_phonemes=input_is_phones) for t in texts]
+        synth = [w.float().cpu().numpy() for w in self.synthesize_batch(feats, input_is_phones=input_is_phones, **synthesis_keywords)]
+        durations = [d.cpu().numpy() for d in self.last_durations]
+        host = [f.float().cpu().numpy() for f in feats]
+        reports = self._prominence().measure(synth, self.SAMPLE_RATE, host, durations=durations, weights=weights, band=band)
+        results = [{"report": r, "words": prosody.word_spans(f), "durations": d} for r, f, d in zip(reports, host, durations)]
+        if keep_waves:
+            for r, w in zip(results, synth):
+                r["synth"] = w
+        return results
+
     def synthesize_ensemble(self, text, utterance_embeddings, durations=None, pitch=None, energy=None, input_is_phones=True, z_noise=None,
                             sample_rate=None, pcm16=False, loudness=None, peak_ceiling=-1.0, speech_level=None, true_peak_ceiling=None,
                             limiter=False):
@@ -680,7 +721,7 @@ class ToucanTTSInterface(torch.nn.Module):
     def synthesize_grid(self, text, duration_scaling_factors=(1.0,), pitch_variance_scales=(1.0,), energy_variance_scales=(1.0,),
                         pause_duration_scaling_factors=(1.0,), input_is_phones=True, utterance_embedding=None, durations=None, pitch=None,
                         energy=None, z_noise=None, sample_rate=None, pcm16=False, curves=None, loudness=None, peak_ceiling=-1.0,
-                        speech_level=None, check_pronunciation=False, beam=8, true_peak_ceiling=None, limiter=False):
+                        speech_level=None, check_pronunciation=False, beam=8, true_peak_ceiling=None, limiter=False, word_prominence=False):
         """Additive API: ONE text (a phoneme string, or its [L, 62] feature tensor) at every combination of the four tuples of prosody scales - the Cartesian product in row-major
         order of the tuples as listed (the pause factor varies fastest) - synthesised as ragged batches of at most MAX_FILE_BATCH
         variants with per-utterance scales instead of one pass per setting.  Returns one dict per variant, in that order:
@@ -706,7 +747,11 @@ class ToucanTTSInterface(torch.nn.Module):
         ``check_pronunciation`` / ``beam``: every dict gains ``pronunciation``, what ``check_pronunciation`` returns for that variant
         alone (the 24 kHz float waveform as synthesised, before ``loudness`` / ``speech_level`` / ``sample_rate``): phoneme error rate
         and minimum goodness of pronunciation against the scales or the emphasised word - how far a knob goes before the words
-        break, in the aligner's opinion."""
+        break, in the aligner's opinion.
+        ``word_prominence``: every dict gains ``prominence``, the float64 [words, 8] report of ``word_prominence`` for that variant
+        alone (the 24 kHz float waveform as synthesised, the durations the variant was synthesised with).  With the emphasis sweep
+        as ``curves`` the reports form the matrix "word stressed x word measured": did the stressed word come out stressed, and
+        how far can its factors be lowered before it no longer does."""
         self._check_output_format(sample_rate, pcm16)
         if check_pronunciation:
             from . import pronunciation
@@ -741,9 +786,13 @@ class ToucanTTSInterface(torch.nn.Module):
                                                          durations=rep(durations), pitch=rep(pitch), energy=rep(energy),
                                                          **{name: [v[k] for v in chunk] for k, name in enumerate(prosody.KNOBS)}, **kw)
                 before, after = self.last_prosody_stats
-                checked = None
-                if check_pronunciation:
+                checked = measured = None
+                if check_pronunciation or word_prominence:
                     host24 = wav24.float().cpu().numpy()
+                if word_prominence:
+                    measured = self._prominence().measure([host24[b:b + m] for b, m in spans24], self.SAMPLE_RATE, [phones.float().cpu().numpy()] * n,
+                                                          durations=[d.cpu().numpy() for d in self.last_durations])
+                if check_pronunciation:
                     checked = self._checker().check([phones.float().cpu().numpy()] * n, [host24[b:b + m] for b, m in spans24], self.SAMPLE_RATE, beam=beam)
                 wav24 = self._normalize(wav24, spans24, loudness, peak_ceiling, speech_level, true_peak_ceiling, limiter)
                 if normalise:
@@ -758,6 +807,8 @@ class ToucanTTSInterface(torch.nn.Module):
                                     "stats_before": before[i], "stats_after": after[i]})
                     if checked is not None:
                         results[-1]["pronunciation"] = checked[i]
+                    if measured is not None:
+                        results[-1]["prominence"] = measured[i]
                     if normalise:
                         results[-1]["loudness"] = rows[-1][i]
                     if delivery:
