@@ -160,8 +160,7 @@ __global__ __launch_bounds__(64) void level_kernel(const double* __restrict__ sq
   for (int64_t k0 = 0; k0 < n_slots; k0 += 64) {
     const int64_t k = k0 + lane;
     const double v = k < n_slots ? sq[row0 + k] : 0.0;
-    const int steps = (int)min((int64_t)64, n_slots - k0);
-    for (int i = 0; i < steps; ++i) total += __shfl(v, i, 64);
+    wave_each_in_order((int)min((int64_t)64, n_slots - k0), [&](int, double vi) { total += vi; }, v);
   }
 
   const double ninf = -INFINITY, margin = 15.9;
@@ -242,10 +241,8 @@ __global__ __launch_bounds__(64) void runs_kernel(const int32_t* __restrict__ po
       f = pp[k * AC_POS + 0];
       l = pp[k * AC_POS + 1];
     }
-    const int steps = (int)min((int64_t)64, n_slots - k0);
-    for (int i = 0; i < steps; ++i) {
-      const int fi = __shfl(f, i, 64), li = __shfl(l, i, 64);
-      if (fi < 0) continue;
+    wave_each_in_order((int)min((int64_t)64, n_slots - k0), [&](int i, int fi, int li) {
+      if (fi < 0) return;
       const int64_t at = (k0 + i) * S + fi;
       if (run_begin < 0) {
         run_begin = at;
@@ -254,7 +251,7 @@ __global__ __launch_bounds__(64) void runs_kernel(const int32_t* __restrict__ po
         run_begin = at;
       }
       last_at = (k0 + i) * S + li;
-    }
+    }, f, l);
   }
   if (run_begin >= 0) close();
   if (lane == 0) {

@@ -129,18 +129,7 @@ int lstm_step(const float* xproj, int ldx, const float* w_hh_blk, const float* h
 // the output itself by thread 0.
 constexpr int MAS_THREADS = 256;
 
-__device__ inline float block_max(float v, float* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int o = MAS_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
+static_assert(MAS_THREADS == 256, "block_tree_fold is a tree over 256 threads");
 
 __global__ __launch_bounds__(MAS_THREADS) void mas_durations_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ frame_begin,
                                                                     const int* __restrict__ n_frames, const int* __restrict__ ids,
@@ -180,7 +169,7 @@ __global__ __launch_bounds__(MAS_THREADS) void mas_durations_kernel(const float*
     const int i = (int)(c / L), j = (int)(c % L);
     m = fmaxf(m, fabsf(logits[(size_t)(fb + i) * ld + tok[j]]));
   }
-  const float m1 = block_max(m, red) + 1.0f;  // alignment_prob + (max|p| + 1.0): the offset is formed first, as float32
+  const float m1 = block_tree_fold(m, red, [](float a, float b) { return fmaxf(a, b); }) + 1.0f;  // alignment_prob + (max|p| + 1.0): the offset is formed first, as float32
 
   // row 0 (Aligner.py:211-213): log_p[0, 0] = log(p + M + 1), -inf elsewhere
   float* prev = rows;
@@ -262,7 +251,7 @@ __global__ __launch_bounds__(256) void frame_energy_kernel(const float* __restri
     const float re = xr[c], im = xr[bins + c];
     s += re * re + im * im;
   }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if (lane == 0) y[r] = sqrtf(fmaxf(s, 1.0e-10f));
 }
 

@@ -198,26 +198,7 @@ __device__ __forceinline__ float glow_mix_value(const float (&w)[16], int o, flo
   return (z - an_bias) * an_scale;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Sum over a workgroup of 256: the butterfly within each wavefront, then the four wavefronts added 0 + 1 + 2 + 3.  red: 4 floats of
-// LDS.  Every thread of the workgroup must call it (two barriers), and all get the same sum.
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 }  // namespace tts
+
+// the cross-lane reductions and scans (wave_sum, block_sum, wave_max, ...): kept reachable through this header for its users
+#include "wave_ops.h"

@@ -66,21 +66,20 @@ __device__ __forceinline__ float amplitude(float re, float im) {
   return __fsqrt_rn(p < 1e-10f ? 1e-10f : p);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// The NS sums of the workgroup, left in red[q][wavefront]; thread 0 adds the wavefronts ((0 + 1) + 2) + 3 after the barrier it
-// returns behind.  Every thread calls it.
-__device__ __forceinline__ void block_sums(double (&s)[NS], double (*red)[4]) {
+// The NS sums of the workgroup in the butterfly order of wave_ops.h, left in red[q][wavefront]; thread 0 folds the wavefronts
+// (fold_sums) after the ONE barrier this returns behind: the wavefront layer and not block_sum, whose barrier before the write
+// the callers' own barriers stand in for (see there).  Every thread calls it.
+__device__ __forceinline__ void wave_partials(double (&s)[NS], double (*red)[4]) {
 #pragma unroll
   for (int q = 0; q < NS; ++q) {
-    s[q] = wave_sum_f64(s[q]);
+    s[q] = wave_sum(s[q]);
     if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s[q];
   }
   __syncthreads();
+}
+
+__device__ __forceinline__ double fold_sums(const double* red) {
+  return fold_left(red, [](double a, double b) { return a + b; });
 }
 
 __global__ __launch_bounds__(FD_THREADS) void spectral_distance_kernel(const float* __restrict__ spec, int64_t ld, int bins, int64_t total_rows,
@@ -133,13 +132,13 @@ __global__ __launch_bounds__(FD_THREADS) void spectral_distance_kernel(const flo
       const double ga = (double)ea, gb = (double)eb;
       s[0] = fabs(log10(ga < 1e-10 ? 1e-10 : ga) - log10(gb < 1e-10 ? 1e-10 : gb));
     }
-    block_sums(s, red);
+    wave_partials(s, red);
     if (tid == 0) {
       double* out = frame_sums + ((int64_t)p * max_frames + f) * NS;
 #pragma unroll
-      for (int q = 0; q < NS; ++q) out[q] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
+      for (int q = 0; q < NS; ++q) out[q] = fold_sums(red[q]);
     }
-    // the next frame's amplitudes are written behind block_sums' barrier (every band is done with these) and its `red` behind
+    // the next frame's amplitudes are written behind wave_partials' barrier (every band is done with these) and its `red` behind
     // the barrier after them (thread 0 has read these by then)
   }
 }
@@ -156,10 +155,10 @@ __global__ __launch_bounds__(FD_THREADS) void spectral_reduce_kernel(const doubl
 #pragma unroll
     for (int q = 0; q < NS; ++q) s[q] += rows[f * NS + q];
   }
-  block_sums(s, red);
+  wave_partials(s, red);  // (the only use of red in this kernel)
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int q = 0; q < NS; ++q) totals[(int64_t)p * NS + q] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
+    for (int q = 0; q < NS; ++q) totals[(int64_t)p * NS + q] = fold_sums(red[q]);
   }
 }
 

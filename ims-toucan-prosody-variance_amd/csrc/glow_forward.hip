@@ -139,7 +139,7 @@ int glow_forward_rows(float* x, int ldx, int rows, const float* ml, int ld_ml, d
 }
 
 // ---- the glow loss of each utterance from its latent rows, one workgroup per utterance -----------------------------------------
-// Wave v takes the utterance's rows v, v + 4, ...: 40 lanes square a row's 160 values in fp64, a butterfly adds them, lane 0 adds the
+// Wave v takes the utterance's rows v, v + 4, ...: 40 lanes square a row's 160 values in fp64, wave_sum (wave_ops.h) adds them, lane 0 adds the
 // row's two parts to the wave's sums; thread 0 adds the four waves' sums in order.  Nothing depends on the batch.
 constexpr double HALF_LOG_2PI = 0.91893853320467274178;
 
@@ -159,8 +159,7 @@ __global__ __launch_bounds__(GF_THREADS) void glow_nll_reduce_kernel(const float
       const float4 v = ld4<VEC>(z + r * ldz + 4 * lane);
       q = ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    q = wave_sum(q);
     q = 0.5 * q + GF_C * HALF_LOG_2PI;
     const double l = row_logdet[r];
     if (lane == 0 && row_parts) {

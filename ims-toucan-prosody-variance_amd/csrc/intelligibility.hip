@@ -43,12 +43,6 @@ __device__ __forceinline__ StoiPair load_stoi_pair(const int64_t* __restrict__ p
   return r;
 }
 
-__device__ __forceinline__ double st_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // the larger of the two; a NaN on either side stays
 __device__ __forceinline__ double st_max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
 
@@ -68,7 +62,7 @@ __global__ __launch_bounds__(ST_THREADS) void frame_energy_kernel(const float* _
     const double v = (double)__fmul_rn(window[lane + 64 * k], src[lane + 64 * k]);
     s = fma(v, v, s);  // (the square of an fp32 value is exact in fp64)
   }
-  s = st_wave_sum(s);
+  s = wave_sum(s);
   if (lane == 0) energy[(int64_t)p * max_frames + f] = s;
 }
 
@@ -82,11 +76,11 @@ __global__ __launch_bounds__(ST_THREADS) void select_kernel(const double* __rest
   int* __restrict__ out = kept + (int64_t)p * max_frames;
   double mx = -INFINITY;
   for (int64_t f = tid; f < F; f += ST_THREADS) mx = st_max_nan(mx, st_level_db(e[f]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = st_max_nan(mx, __shfl_xor(mx, o, 64));
+  // the butterfly and the left fold of wave_ops.h with one barrier: top is written once, before any other barrier of the kernel
+  mx = wave_fold(mx, st_max_nan);
   if (lane == 0) top[wv] = mx;
   __syncthreads();
-  mx = st_max_nan(st_max_nan(st_max_nan(top[0], top[1]), top[2]), top[3]);
+  mx = fold_left(top, st_max_nan);
   const double threshold = mx - ST_RANGE_DB;
   int64_t run = 0;  // frames kept in the sweeps before this one (uniform)
   for (int64_t f0 = 0; f0 < F; f0 += ST_THREADS) {
@@ -272,14 +266,14 @@ __global__ __launch_bounds__(ST_THREADS) void stoi_reduce_kernel(const double* _
   }
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
-    s[q] = st_wave_sum(s[q]);
+    s[q] = wave_sum(s[q]);
     if ((tid & 63) == 0) red[q][tid >> 6] = s[q];
   }
-  __syncthreads();
+  __syncthreads();  // one barrier: the only use of red in this kernel
   if (tid == 0) {
 #pragma unroll
     for (int q = 0; q < 2; ++q)
-      totals[2 * (int64_t)p + q] = S > 0 ? (red[q][0] + red[q][1] + red[q][2] + red[q][3]) / (double)S : (double)NAN;
+      totals[2 * (int64_t)p + q] = S > 0 ? fold_left(red[q], [](double a, double b) { return a + b; }) / (double)S : (double)NAN;
   }
 }
 

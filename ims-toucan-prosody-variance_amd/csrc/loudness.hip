@@ -97,23 +97,7 @@ __global__ __launch_bounds__(64) void gate_kernel(const double* __restrict__ ene
 
   // the mean of the z_j above `thr`, in index order; also their number and the largest z_j of all
   auto gated = [&](double thr, double& sum, int64_t& kept, double& z_max) {
-    sum = 0.0;
-    kept = 0;
-    z_max = 0.0;
-    for (int64_t j0 = 0; j0 < n_blocks; j0 += 64) {
-      const int64_t j = j0 + lane;
-      double z = 0.0;
-      if (j < n_blocks) z = (((e[j] + e[j + 1]) + e[j + 2]) + e[j + 3]) / per;
-      const int steps = (int)min((int64_t)64, n_blocks - j0);
-      for (int i = 0; i < steps; ++i) {
-        const double zi = __shfl(z, i, 64);
-        z_max = fmax(z_max, zi);
-        if (zi > thr) {
-          sum += zi;
-          ++kept;
-        }
-      }
-    }
+    gated_walk(n_blocks, lane, thr, [&](int64_t j) { return (((e[j] + e[j + 1]) + e[j + 2]) + e[j + 3]) / per; }, sum, kept, z_max);
   };
   double sum_abs, sum_both = 0.0, z_max, unused;
   int64_t n_abs, n_both = 0;

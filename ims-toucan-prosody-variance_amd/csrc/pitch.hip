@@ -30,31 +30,13 @@ constexpr double P_PI = 3.14159265358979323846;
 constexpr double P_GOLD = 0.61803398874989484820;  // (sqrt(5) - 1) / 2
 constexpr int P_GOLD_STEPS = 45;                   // 2 * P_GOLD^45 < 1e-9
 
-// fixed-order trees over the workgroup's 256 values
-__device__ inline double block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int o = P_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
+// the workgroup's 256 values in the LDS tree's order (wave_ops.h block_tree_fold: not the butterfly's)
+static_assert(P_THREADS == 256, "block_tree_fold is a tree over 256 threads");
+__device__ inline double tree_sum(double v, double* red) {
+  return block_tree_fold(v, red, [](double a, double b) { return a + b; });
 }
-
-__device__ inline float block_maxf(float v, float* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int o = P_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
+__device__ inline float tree_maxf(float v, float* red) {
+  return block_tree_fold(v, red, [](float a, float b) { return fmaxf(a, b); });
 }
 
 // ---- mean and peak of every utterance, one workgroup each ------------------------------------------------------------------------
@@ -65,10 +47,10 @@ __global__ __launch_bounds__(P_THREADS) void wave_stats_kernel(const float* __re
   const float* x = wave + wave_begin[b];
   double s = 0.0;
   for (int i = tid; i < n; i += P_THREADS) s += (double)x[i];
-  const float mean = n > 0 ? (float)(block_sum(s, red) / (double)n) : 0.0f;
+  const float mean = n > 0 ? (float)(tree_sum(s, red) / (double)n) : 0.0f;
   float m = 0.0f;
   for (int i = tid; i < n; i += P_THREADS) m = fmaxf(m, fabsf(x[i] - mean));  // the subtraction the candidates kernel repeats
-  m = block_maxf(m, reinterpret_cast<float*>(red));
+  m = tree_maxf(m, reinterpret_cast<float*>(red));
   if (tid == 0) {
     stats[2 * b] = mean;
     stats[2 * b + 1] = m;
@@ -84,7 +66,7 @@ int wave_stats(const float* wave, const int* wave_begin, const int* n_samples, i
 
 // ---- candidates of one frame ---------------------------------------------------------------------------------------------------
 // S_D(x): Hann-windowed sinc interpolation of r[-599 .. 599] (r[-k] = r[k]) over at most `depth` samples either side of x, by one
-// whole wavefront: lane-strided terms, then a fixed butterfly.  sin(pi (x - m)) is (-1)^k sin(pi frac) for the k-th sample on
+// whole wavefront: lane-strided terms, then wave_sum (wave_ops.h).  sin(pi (x - m)) is (-1)^k sin(pi frac) for the k-th sample on
 // either side, so one sine serves every term.  Every lane returns the sum.
 __device__ inline double sinc_wave(const double* r, double x, int depth) {
   const int lane = threadIdx.x & 63;
@@ -104,9 +86,7 @@ __device__ inline double sinc_wave(const double* r, double x, int depth) {
     const double s = (k & 1) ? -(left ? sl : sr) : (left ? sl : sr);
     sum += r[abs(m)] * s / a * (0.5 + 0.5 * cos(a / (left ? wl : wr)));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  return sum;
+  return wave_sum(sum);
 }
 
 // Ordered compaction by one wavefront: list[] <- the indices i in [lo, hi) with pred(i), ascending, at most `cap` of them; every
@@ -172,14 +152,14 @@ __global__ __launch_bounds__(P_THREADS) void pitch_candidates_kernel(const float
     seg[j] = v;
     if (j >= P_HW - P_NPER && j < P_HW + P_NPER) s += (double)v;
   }
-  const float lmean = (float)(block_sum(s, red) / (double)(2 * P_NPER));
+  const float lmean = (float)(tree_sum(s, red) / (double)(2 * P_NPER));
   float lp = 0.0f;
   for (int j = tid; j < P_NW; j += P_THREADS) {
     const float v = (seg[j] - lmean) * win[j];
     seg[j] = v;
     if (j >= P_HW - P_HPER && j < P_HW + P_HPER) lp = fmaxf(lp, fabsf(v));
   }
-  lp = block_maxf(lp, reinterpret_cast<float*>(red));  // its barriers also publish seg
+  lp = tree_maxf(lp, reinterpret_cast<float*>(red));  // its barriers also publish seg
   const float intensity = gpeak > 0.0f ? fminf(1.0f, lp / gpeak) : 0.0f;
 
   // ac[k] = sum_j seg[j] seg[j + k]: thread (slice p, group g) keeps the lags 8g .. 8g + 7 in registers over the samples of its
@@ -302,7 +282,7 @@ int pitch_candidates(const float* wave, const int* wave_begin, const int* n_samp
 
 // ---- the path: Viterbi over the candidates of an utterance, one workgroup each -------------------------------------------------
 // Thread (c, p) = (tid / 16, tid % 16) holds the transition from candidate p of frame t - 1 to candidate c of frame t; the 16 lanes
-// of a candidate reduce to the first maximum by a fixed butterfly.  Per candidate of a frame, info = (log2 f or -1 when voiceless,
+// of a candidate reduce to the first maximum by wave_arg_max (wave_ops.h).  Per candidate of a frame, info = (log2 f or -1 when voiceless,
 // local value); the first 16 threads prepare frame t + 1 while the transitions of frame t are taken.  Back-pointers: one byte per
 // candidate, 16 per frame (byte 15 later holds the chosen candidate), in LDS or in the caller's scratch.
 constexpr int PATH_ROW = 16;
@@ -385,15 +365,7 @@ __global__ __launch_bounds__(P_THREADS) void pitch_path_kernel(const float* __re
     const double cost = (up && uc) ? 0.0 : (up != uc) ? P_VUV * corr : P_JUMP * corr * fabs(ip.lf - ic.lf);
     double val = delta[prev][p] - cost;  // -inf from a candidate that is not there
     int idx = p;
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {  // the first maximum of the 16 lanes
-      const double ov = __shfl_xor(val, o, 16);
-      const int oi = __shfl_xor(idx, o, 16);
-      if (ov > val || (ov == val && oi < idx)) {
-        val = ov;
-        idx = oi;
-      }
-    }
+    wave_arg_max<16>(val, idx);  // the first maximum of the 16 lanes
     if (p == 0) {
       delta[cur][c] = val + ic.local;
       bp[(size_t)t * PATH_ROW + c] = (unsigned char)idx;

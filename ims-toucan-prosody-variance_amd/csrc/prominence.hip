@@ -23,7 +23,7 @@ constexpr int PM_MAX_TAPS = TTS_PROMINENCE_MAX_TAPS, PM_TABLE_LD = TTS_PROMINENC
 constexpr int PM_MAX_HALO = (PM_MAX_TAPS - 1) / 2;          // 8 s_5 = 512 frames on either side
 constexpr int PM_WINDOW = PM_THREADS + 2 * PM_MAX_HALO;     // 1280 frames of a channel in LDS at the widest scale
 constexpr int PM_NONE = INT_MAX;                            // "no valid frame to the right" (exact as a double)
-static_assert(PM_THREADS == 256 && PM_WAVES == 4, "the reductions below add four wavefronts");
+static_assert(PM_THREADS == 256 && PM_WAVES == 4, "the reductions (wave_ops.h) fold four wavefronts");
 
 struct PmUtt {
   int64_t first, T, ph0, nph, un0, nun;
@@ -38,57 +38,6 @@ __device__ __forceinline__ PmUtt load_pm_utt(const int64_t* __restrict__ utts, i
                   (n_phones < 0 || (v.ph0 >= 0 && v.nph >= 0 && v.nph <= n_phones && v.ph0 <= n_phones - v.nph)) &&
                   (n_units < 0 || (v.un0 >= 0 && v.nun >= 0 && v.nun <= n_units && v.un0 <= n_units - v.nun));
   if (!ok) v.T = v.nph = v.nun = 0;
-  return v;
-}
-
-__device__ __forceinline__ double pm_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Sum over the workgroup: the butterfly, then the wavefronts as ((0 + 1) + 2) + 3.  Every thread calls it; all get the sum.
-__device__ __forceinline__ double pm_block_sum(double v, double* red) {
-  v = pm_wave_sum(v);
-  __syncthreads();  // red may still be read from the call before
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// Inclusive max-scan over the workgroup in thread order (what thread i gets: the maximum of threads 0 .. i); *all = of all 256.
-__device__ __forceinline__ int pm_scan_max_forward(int v, int* red, int* all) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int n = __shfl_up(v, o, 64);
-    if (lane >= o) v = max(v, n);
-  }
-  __syncthreads();
-  if (lane == 63) red[wv] = v;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < PM_WAVES; ++k)
-    if (k < wv) v = max(v, red[k]);
-  *all = max(max(red[0], red[1]), max(red[2], red[3]));
-  return v;
-}
-
-// Inclusive min-scan from the last thread down (thread i gets the minimum of threads i .. 255); *all = of all 256.
-__device__ __forceinline__ int pm_scan_min_backward(int v, int* red, int* all) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int n = __shfl_down(v, o, 64);
-    if (lane + o < 64) v = min(v, n);
-  }
-  __syncthreads();
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < PM_WAVES; ++k)
-    if (k > wv) v = min(v, red[k]);
-  *all = min(min(red[0], red[1]), min(red[2], red[3]));
   return v;
 }
 
@@ -138,10 +87,11 @@ __global__ __launch_bounds__(PM_THREADS) void prominence_channels_kernel(const f
   // the energy floor: the maximum does not depend on an order
   float top = 0.0f;
   for (int t = tid; t < T; t += PM_THREADS) top = fmaxf(top, enu[t]);
+  // one barrier (red_f is written once in this kernel); the left fold equals the (0,1),(2,3) one: top >= 0 and never a NaN
   top = wave_max(top);
   if ((tid & 63) == 0) red_f[tid >> 6] = top;
   __syncthreads();
-  top = fmaxf(fmaxf(red_f[0], red_f[1]), fmaxf(red_f[2], red_f[3]));
+  top = fold_left(red_f, [](float a, float b) { return fmaxf(a, b); });
   const double lowest = (double)FLT_MIN, scaled = 1e-3 * (double)top;
   const double floor_e = scaled > lowest ? scaled : lowest;
   for (int c = 0; c < PM_CH; ++c) {
@@ -153,7 +103,7 @@ __global__ __launch_bounds__(PM_THREADS) void prominence_channels_kernel(const f
       double v;
       const bool in = t < T, valid = in && pm_value(c, t, f0u, enu, ph, utt.nph, floor_e, &v);
       int all;
-      const int r = min(pm_scan_min_backward(valid ? t : PM_NONE, red_i, &all), carry);
+      const int r = min(block_scan_backward(valid ? t : PM_NONE, red_i, &all, [](int a, int b) { return min(a, b); }), carry);
       if (in) xc[t] = valid ? v : (double)r;
       carry = min(carry, all);
     }
@@ -165,7 +115,7 @@ __global__ __launch_bounds__(PM_THREADS) void prominence_channels_kernel(const f
       double v;
       const bool in = t < T, valid = in && pm_value(c, t, f0u, enu, ph, utt.nph, floor_e, &v);
       int all;
-      const int l = max(pm_scan_max_forward(valid ? t : -1, red_i, &all), carry);
+      const int l = max(block_scan_forward(valid ? t : -1, red_i, &all, [](int a, int b) { return max(a, b); }), carry);
       if (in && !valid) {
         const int r = (int)xc[t];
         double y = 0.0;
@@ -184,13 +134,13 @@ __global__ __launch_bounds__(PM_THREADS) void prominence_channels_kernel(const f
     __syncthreads();
     double s = 0.0;
     for (int t = tid; t < T; t += PM_THREADS) s += xc[t];
-    const double mean = pm_block_sum(s, red_d) / (double)T;
+    const double mean = block_sum(s, red_d) / (double)T;
     s = 0.0;
     for (int t = tid; t < T; t += PM_THREADS) {
       const double d = xc[t] - mean;
       s += d * d;
     }
-    const double sd = sqrt(pm_block_sum(s, red_d) / (double)T);
+    const double sd = sqrt(block_sum(s, red_d) / (double)T);
     const double am = fabs(mean);
     const bool flat = !(sd > 1e-12 * (am > 1.0 ? am : 1.0));
     for (int t = tid; t < T; t += PM_THREADS) xc[t] = flat ? 0.0 : (xc[t] - mean) / sd;  // (its own frames only)
@@ -271,16 +221,8 @@ __global__ __launch_bounds__(PM_THREADS) void prominence_units_kernel(const doub
         at = t;
       }
     }
-    sum = pm_wave_sum(sum);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ob = __shfl_xor(best, o, 64);
-      const int oa = __shfl_xor(at, o, 64);
-      if (ob > best || (ob == best && oa < at)) {
-        best = ob;
-        at = oa;
-      }
-    }
+    sum = wave_sum(sum);
+    wave_arg_max(best, at);
     if (lane == 0) {
       double* row = out + k * PM_COLS;
       const bool found = at != PM_NONE;
@@ -312,15 +254,7 @@ __global__ __launch_bounds__(PM_THREADS) void prominence_units_kernel(const doub
         at = t;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ob = __shfl_xor(best, o, 64);
-      const int oa = __shfl_xor(at, o, 64);
-      if (ob < best || (ob == best && oa < at)) {
-        best = ob;
-        at = oa;
-      }
-    }
+    wave_arg_min(best, at);
     if (lane == 0 && at != PM_NONE) {
       out[k * PM_COLS + 6] = -best;
       out[k * PM_COLS + 7] = (double)at;

@@ -200,7 +200,8 @@ struct Cand {
   int q;
 };
 
-__device__ __forceinline__ bool cand_before(double ta, int qa, double tb, int qb) { return ta > tb || (ta == tb && qa < qb); }
+// the tie rule of wave_arg_max (wave_ops.h), for the serial picks
+__device__ __forceinline__ bool cand_before(double ta, int qa, double tb, int qb) { return arg_before<true>(ta, qa, tb, qb); }
 
 // total of candidate q, or -inf if q is no candidate (blank, dropped, merged into a stay candidate, or without probability)
 __device__ __forceinline__ double cand_total(int q, int S, int blank, const unsigned char* __restrict__ drop, const BeamSet& bs,
@@ -301,12 +302,7 @@ __global__ __launch_bounds__(P_THREADS) void ctc_beam_kernel(const float* __rest
       int k = 0;
       for (; k < W; ++k) {
         Cand w = mine;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const double ot = __shfl_xor(w.tot, o, 64);
-          const int oq = __shfl_xor(w.q, o, 64);
-          if (cand_before(ot, oq, w.tot, w.q)) w = {ot, oq};
-        }
+        wave_arg_max(w.tot, w.q);
         if ((tid & 63) == 0) {
           r_tot[tid >> 6] = w.tot;
           r_q[tid >> 6] = w.q;

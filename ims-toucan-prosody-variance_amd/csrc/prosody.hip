@@ -96,17 +96,9 @@ __global__ __launch_bounds__(256) void prosody_control_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------
-// Statistics.  Every sum is an fp64 sum in one fixed order: thread t adds its rows t, t + 256, ... in turn, the 64 lanes of a
-// wavefront are folded by the xor butterfly (32, 16, ... 1), the four wavefronts are added 0 + 1 + 2 + 3.
+// Statistics.  Every sum is an fp64 sum in one fixed order: thread t adds its rows t, t + 256, ... in turn, then block_sum
+// (wave_ops.h: butterfly + left fold).
 // ------------------------------------------------------------------------------------------------
-__device__ double block_sum_f64(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 __global__ __launch_bounds__(256) void prosody_stats_kernel(const float* __restrict__ pitch, const float* __restrict__ energy,
                                                             const int* __restrict__ dur, const int* __restrict__ seq_begin,
@@ -121,11 +113,11 @@ __global__ __launch_bounds__(256) void prosody_stats_kernel(const float* __restr
     if (e != 0.0f) { se += (double)e; ne += 1.0; }
     fr += (double)dur[r];
   }
-  np = block_sum_f64(np, red);
-  sp = block_sum_f64(sp, red);
-  ne = block_sum_f64(ne, red);
-  se = block_sum_f64(se, red);
-  fr = block_sum_f64(fr, red);
+  np = block_sum(np, red);
+  sp = block_sum(sp, red);
+  ne = block_sum(ne, red);
+  se = block_sum(se, red);
+  fr = block_sum(fr, red);
   const double mp = np > 0.0 ? sp / np : 0.0, me = ne > 0.0 ? se / ne : 0.0;
   double qp = 0.0, qe = 0.0;
   for (int r = r0 + threadIdx.x; r < r1; r += 256) {
@@ -133,8 +125,8 @@ __global__ __launch_bounds__(256) void prosody_stats_kernel(const float* __restr
     if (p != 0.0f) { const double d = (double)p - mp; qp += d * d; }
     if (e != 0.0f) { const double d = (double)e - me; qe += d * d; }
   }
-  qp = block_sum_f64(qp, red);
-  qe = block_sum_f64(qe, red);
+  qp = block_sum(qp, red);
+  qe = block_sum(qe, red);
   if (threadIdx.x == 0) {
     float* o = stats + (size_t)u * TTS_PROSODY_STATS;
     o[0] = (float)np; o[1] = (float)mp; o[2] = (float)(np > 0.0 ? qp / np : 0.0);
@@ -154,31 +146,15 @@ __device__ __forceinline__ long long uniform_i64(long long v) {
   return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
-__device__ long long block_sum_i64(long long v, long long* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return uniform_i64(red[0] + red[1] + red[2] + red[3]);
-}
+// block_sum of wave_ops.h, the result in scalar registers
+__device__ __forceinline__ long long uniform_sum(long long v, long long* red) { return uniform_i64(block_sum(v, red)); }
 
-// Exclusive prefix sum over the 256 threads in thread order; *total: the sum of all.  Every thread calls it.
-__device__ long long block_exclusive_scan_i64(long long v, long long* red, long long* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  long long inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();
-  if (lane == 63) red[w] = inc;
-  __syncthreads();
-  long long off = 0;
-  for (int i = 0; i < w; ++i) off += red[i];
-  *total = uniform_i64(red[0] + red[1] + red[2] + red[3]);
-  return off + inc - v;
+// Exclusive prefix sum over the 256 threads in thread order, the inclusive one minus the thread's own; *total: the sum of all.
+// Every thread calls it.
+__device__ __forceinline__ long long exclusive_prefix(long long v, long long* red, long long* total) {
+  const long long inc = block_scan_forward(v, red, total, [](long long a, long long b) { return a + b; });
+  *total = uniform_i64(*total);
+  return inc - v;
 }
 
 struct FitRows {
@@ -209,7 +185,7 @@ __device__ __forceinline__ int fit_row(const FitRows& q, int r, float x) {
 __device__ long long fit_frames(const FitRows& q, int r0, int r1, float x, long long* red) {
   long long s = 0;
   for (int r = r0 + threadIdx.x; r < r1; r += 256) s += fit_row(q, r, x);
-  return block_sum_i64(s, red);
+  return uniform_sum(s, red);
 }
 
 __global__ __launch_bounds__(256) void prosody_fit_fill_kernel(const int* __restrict__ seq_begin, const int* __restrict__ seq_end,
@@ -297,7 +273,7 @@ __global__ __launch_bounds__(256) void prosody_fit_kernel(const float* __restric
       const int r = base + threadIdx.x;
       const long long delta = r < r1 ? (long long)fit_row(q, r, x1) - (long long)fit_row(q, r, x0) : 0;
       long long total;
-      const long long p = carry + block_exclusive_scan_i64(delta, red, &total);
+      const long long p = carry + exclusive_prefix(delta, red, &total);
       if (r < r1) {
         const int e = (int)(((p + delta) * missing) / n - (p * missing) / n);
         extra[r] = e;
@@ -305,7 +281,7 @@ __global__ __launch_bounds__(256) void prosody_fit_kernel(const float* __restric
       }
       carry += total;
     }
-    extra_rows = block_sum_i64(mine, red);
+    extra_rows = uniform_sum(mine, red);
   }
   if (status != TTS_FIT_EMPTY) {
     if (q.kind == TTS_FIT_SPAN) {

@@ -74,7 +74,7 @@ __device__ __forceinline__ void walk_segments(float (&tile)[2][SEG_TILE], const 
 // Pass 2, one wavefront per utterance: state[u][k] (N doubles) holds end_k and gets s_k, the state at the start of segment k; M is
 // the row-major N x N transition.  WITH_PARTIAL: a trailing partial slot gets its start state too (its own end state is never
 // stored, so none is loaded).  64 segments at a time: every lane loads its segment's end state, then all lanes walk the same chain
-// in order, lane j keeping the s it sees at step j.
+// in order, lane j keeping the s it sees at step j (the in-order walk of wave_ops.h, spelled out here: N values a step).
 template <int N, bool WITH_PARTIAL>
 __global__ __launch_bounds__(64) void segment_carry_kernel(int64_t n_samples, const int64_t* __restrict__ spans, int S,
                                                            const double* __restrict__ transition, int64_t max_segments,
@@ -117,6 +117,28 @@ __global__ __launch_bounds__(64) void segment_carry_kernel(int64_t n_samples, co
 #pragma unroll
       for (int i = 0; i < N; ++i) rows[k * N + i] = mine[i];
     }
+  }
+}
+
+// What the gating meters share (gate_kernel of loudness.hip, loudness_range_kernel of truepeak.hip), one wavefront per utterance: the
+// lanes form z_of(j) of 64 blocks, then every lane takes them in index order (wave_each_in_order) -> the sum and the number of the
+// z_j above thr, and the largest z_j of all.
+template <class Z>
+__device__ __forceinline__ void gated_walk(int64_t n_blocks, int lane, double thr, Z z_of, double& sum, int64_t& kept, double& z_max) {
+  sum = 0.0;
+  kept = 0;
+  z_max = 0.0;
+  for (int64_t j0 = 0; j0 < n_blocks; j0 += 64) {
+    const int64_t j = j0 + lane;
+    double z = 0.0;
+    if (j < n_blocks) z = z_of(j);
+    wave_each_in_order((int)min((int64_t)64, n_blocks - j0), [&](int, double zi) {
+      z_max = fmax(z_max, zi);
+      if (zi > thr) {
+        sum += zi;
+        ++kept;
+      }
+    }, z);
   }
 }
 

@@ -98,11 +98,7 @@ __global__ __launch_bounds__(256) void length_regulate_kernel(const float* __res
     const int i = base + threadIdx.x;
     int v = i < L ? dur[p0 + i] : 0;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int n = __shfl_up(v, o, 64);
-      if (lane >= o) v += n;
-    }
+    v = wave_scan_forward(v, [](int a, int b) { return a + b; });
     if (lane == 63) wsum[wv] = v;
     __syncthreads();
     int add = carry;

@@ -452,15 +452,9 @@ int col_sum(const float* x, int ldx, int rows, int cols, float* out, float* out2
   return launch_status("col_sum");
 }
 
-__device__ inline double block_sum_f64(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {  // fixed-order tree
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  return red[0];
+// the 256 values in the LDS tree's order (wave_ops.h block_tree_fold: not the butterfly's)
+__device__ inline double tree_sum(double v, double* red) {
+  return block_tree_fold(v, red, [](double a, double b) { return a + b; });
 }
 
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ x, long long n, double* __restrict__ partials) {
@@ -469,13 +463,13 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
   const long long b = (long long)blockIdx.x * chunk, e = b + chunk < n ? b + chunk : n;
   double s = 0.0;
   for (long long i = b + threadIdx.x; i < e; i += 256) s += (double)x[i] * (double)x[i];
-  s = block_sum_f64(s, red);
+  s = tree_sum(s, red);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void sumsq_final_kernel(const double* __restrict__ partials, float* __restrict__ norm) {
   __shared__ double red[256];
-  const double s = block_sum_f64(partials[threadIdx.x], red);
+  const double s = tree_sum(partials[threadIdx.x], red);
   if (threadIdx.x == 0) norm[0] = (float)sqrt(s);
 }
 

@@ -77,15 +77,6 @@ __device__ __forceinline__ float tile_peak(const float* __restrict__ x, const Wa
   return m;
 }
 
-// the largest of the workgroup's m, in every thread.  red: 4 floats of LDS.
-__device__ __forceinline__ float block_max(float m, float* red) {
-  m = wave_max(m);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 template <int F>
 __global__ __launch_bounds__(TP_THREADS) void true_peak_kernel(const float* __restrict__ x, int64_t n_samples, const int64_t* __restrict__ spans,
                                                                const float* __restrict__ table, const double* __restrict__ loudness_stats,
@@ -99,6 +90,7 @@ __global__ __launch_bounds__(TP_THREADS) void true_peak_kernel(const float* __re
   if (i0 >= sp.count) return;  // the whole workgroup: before any barrier
   stage_table(tab, table, F);
   const float g = loudness_stats ? (float)loudness_stats[(int64_t)u * TTS_LOUDNESS_COLUMNS + 6] : 1.0f;
+  // (block_max folds the wavefronts left to right where this kernel once paired (0,1),(2,3): the same for m >= 0, never a NaN)
   const float m = block_max(tile_peak<F>(x, sp, i0, g, stage, tab, with_samples != 0), red);
   // |o| >= 0: its bit pattern orders as an unsigned integer the way the value does (a NaN ends above every number and stays)
   if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned int*>(true_peak) + u, __float_as_uint(m));
@@ -208,31 +200,17 @@ __global__ __launch_bounds__(LRA_THREADS) void loudness_range_kernel(const doubl
   for (int64_t k = lane; k < n_slots; k += LRA_THREADS) pk = fmaxf(pk, p[k]);
   pk = wave_max(pk);
 
-  // the sum of the zs_j above `thr` in index order, their number and the largest zs_j of all (as gate_kernel of loudness.hip)
+  // the sum of the zs_j above `thr` in index order, their number and the largest zs_j of all (gated_walk of segment_scan.h, as gate_kernel of loudness.hip)
   const bool in_lds = n_blocks <= LRA_KEPT;
   auto z_at = [&](int64_t j) { return in_lds ? kept_zs[j] : short_term(e, j, per); };
   auto gated = [&](double thr, double& sum, int64_t& kept, double& z_max, bool first) {
-    sum = 0.0;
-    kept = 0;
-    z_max = 0.0;
-    for (int64_t j0 = 0; j0 < n_blocks; j0 += LRA_THREADS) {
-      const int64_t j = j0 + lane;
-      double z = 0.0;
-      if (j < n_blocks) {
-        z = first ? short_term(e, j, per) : z_at(j);
-        if (first && in_lds) kept_zs[j] = z;
-        if (first && zs) zs[(int64_t)u * max_segments + j] = z;
-      }
-      const int steps = (int)min((int64_t)LRA_THREADS, n_blocks - j0);
-      for (int i = 0; i < steps; ++i) {
-        const double zi = __shfl(z, i, 64);
-        z_max = fmax(z_max, zi);
-        if (zi > thr) {
-          sum += zi;
-          ++kept;
-        }
-      }
-    }
+    auto z_of = [&](int64_t j) {
+      const double z = first ? short_term(e, j, per) : z_at(j);
+      if (first && in_lds) kept_zs[j] = z;
+      if (first && zs) zs[(int64_t)u * max_segments + j] = z;
+      return z;
+    };
+    gated_walk(n_blocks, lane, thr, z_of, sum, kept, z_max);
   };
   double sum_abs, unused_sum, z_max, unused_max, thr = z_abs;
   int64_t n_abs, n_both = 0;
@@ -248,6 +226,7 @@ __global__ __launch_bounds__(LRA_THREADS) void loudness_range_kernel(const doubl
   // the rank is fixed.  Counts are integers: the outcome is the sort's.
   auto select = [&](int64_t rank) {
     unsigned long long prefix = 0, mask = 0;
+#pragma unroll 1  // eight passes over one body, as it was compiled before the scan moved to wave_ops.h (unrolled: 2.4 x the code)
     for (int shift = 56; shift >= 0; shift -= 8) {
       __syncthreads();
       for (int d = lane; d < 256; d += LRA_THREADS) hist[d] = 0;
@@ -263,12 +242,7 @@ __global__ __launch_bounds__(LRA_THREADS) void loudness_range_kernel(const doubl
       unsigned int c[4], mine = 0;
 #pragma unroll
       for (int q = 0; q < 4; ++q) mine += c[q] = hist[4 * lane + q];
-      unsigned int upto = mine;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned int v = __shfl_up(upto, o, 64);
-        if (lane >= o) upto += v;
-      }
+      const unsigned int upto = wave_scan_forward(mine, [](unsigned int a, unsigned int b) { return a + b; });
       const int64_t before = (int64_t)(upto - mine);
       int d = 4 * lane;
       int64_t left = rank - before;

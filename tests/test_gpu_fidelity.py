@@ -158,6 +158,67 @@ def test_spectral_distance_and_reduce_against_float64(bins):
         assert np.array_equal(alone_totals[0].view(np.uint64), batch_totals[i].view(np.uint64)), i
 
 
+def butterfly_order_sum(rows):
+    """float64 [F, 4] -> [4]: the column sums in the order of tts_spectral_reduce, one plain fp64 add per step: thread t adds rows
+    t, t + 256, ... in turn, the 64 lanes of a wavefront are folded by the xor butterfly 32 .. 1, the four wavefronts left to right."""
+    s = np.zeros((256, rows.shape[1]))
+    for f0 in range(0, len(rows), 256):
+        chunk = rows[f0: f0 + 256]
+        s[: len(chunk)] += chunk
+    lanes = np.arange(256)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = s + s[lanes ^ o]
+    return ((s[0] + s[64]) + s[128]) + s[192]
+
+
+def sequential_order_sum(rows):
+    s = np.zeros(rows.shape[1])
+    for r in rows:
+        s = s + r
+    return s
+
+
+def tree_order_sum(rows):
+    """The same per-thread partial sums folded by the 256-entry tree (128 pairs, then 64, ... 1) instead."""
+    s = np.zeros((256, rows.shape[1]))
+    for f0 in range(0, len(rows), 256):
+        chunk = rows[f0: f0 + 256]
+        s[: len(chunk)] += chunk
+    o = 128
+    while o:
+        s[:o] = s[:o] + s[o: 2 * o]
+        o //= 2
+    return s[0]
+
+
+def test_spectral_reduce_adds_in_the_documented_order():
+    """tts_spectral_reduce on given frame sums equals the numpy emulation of its documented order (strided per-thread sums, xor
+    butterfly, four wavefronts left to right) bit for bit.  The values spread over 40 binary orders of magnitude, so another order
+    shows: on the host, before the GPU is touched, every case of more than one wavefront differs from the plain sequential sum and
+    from the 256-entry tree in at least one column (up to 64 frames the tree and the butterfly add the same pairs)."""
+    frames = (1, 64, 65, 255, 256, 257, 1000)
+    rng = np.random.default_rng(20261021)
+    cases = [rng.normal(size=(F, 4)) * 2.0 ** rng.integers(-20, 21, size=(F, 4)) for F in frames]
+    want = np.stack([butterfly_order_sum(c) for c in cases])
+    for F, c, w in zip(frames, cases, want):
+        if F >= 65:
+            assert (sequential_order_sum(c).view(np.int64) != w.view(np.int64)).any(), F
+            assert (tree_order_sum(c).view(np.int64) != w.view(np.int64)).any(), F
+    m = measure()
+    max_frames = max(frames)
+    frame_sums = np.full((len(frames), max_frames, capi.FIDELITY_SUMS), np.nan)  # what lies past a pair's frames is not read
+    for k, c in enumerate(cases):
+        frame_sums[k, : len(c)] = c
+    pairs = np.array([(0, 0, F) for F in frames], dtype=np.int64)  # the reduce reads the frame counts alone
+    fs_d, pr_d = torch.from_numpy(frame_sums).to(DEV), torch.from_numpy(pairs).to(DEV)
+    totals = torch.empty((len(frames), capi.FIDELITY_SUMS), dtype=torch.float64, device=DEV)
+    capi.check(m.lib.tts_spectral_reduce(fs_d.data_ptr(), pr_d.data_ptr(), len(frames), max_frames, totals.data_ptr(), m.ops.stream()),
+               "tts_spectral_reduce")
+    torch.cuda.synchronize()
+    got = totals.cpu().numpy()
+    assert np.array_equal(got.view(np.int64), want.view(np.int64)), (got, want)
+
+
 # ---- the whole measure -------------------------------------------------------------------------------------------------------------
 def test_end_to_end_against_the_reference_golden():
     """The seeded pairs of the golden through SpectralDistance.distance against the reference's stored losses.  The bound is 4 x the
