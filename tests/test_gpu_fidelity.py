@@ -17,6 +17,7 @@ import ims_toucan_prosody_variance_amd  # noqa: F401
 from ims_toucan_prosody_variance_amd import align, capi, fidelity, fixture_weights as fw, resample, style
 from ims_toucan_prosody_variance_amd.ragged import Ragged
 from tests import fidelity_ref as fr
+from tests.wave_order import butterfly_order_sum, sequential_order_sum, tree_order_sum
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -156,39 +157,6 @@ def test_spectral_distance_and_reduce_against_float64(bins):
         alone_frames, alone_totals = run_tail(cases, bins, [i], with_mel, pad=0)
         assert np.array_equal(alone_frames[0].view(np.uint64), batch_frames[i].view(np.uint64)), i
         assert np.array_equal(alone_totals[0].view(np.uint64), batch_totals[i].view(np.uint64)), i
-
-
-def butterfly_order_sum(rows):
-    """float64 [F, 4] -> [4]: the column sums in the order of tts_spectral_reduce, one plain fp64 add per step: thread t adds rows
-    t, t + 256, ... in turn, the 64 lanes of a wavefront are folded by the xor butterfly 32 .. 1, the four wavefronts left to right."""
-    s = np.zeros((256, rows.shape[1]))
-    for f0 in range(0, len(rows), 256):
-        chunk = rows[f0: f0 + 256]
-        s[: len(chunk)] += chunk
-    lanes = np.arange(256)
-    for o in (32, 16, 8, 4, 2, 1):
-        s = s + s[lanes ^ o]
-    return ((s[0] + s[64]) + s[128]) + s[192]
-
-
-def sequential_order_sum(rows):
-    s = np.zeros(rows.shape[1])
-    for r in rows:
-        s = s + r
-    return s
-
-
-def tree_order_sum(rows):
-    """The same per-thread partial sums folded by the 256-entry tree (128 pairs, then 64, ... 1) instead."""
-    s = np.zeros((256, rows.shape[1]))
-    for f0 in range(0, len(rows), 256):
-        chunk = rows[f0: f0 + 256]
-        s[: len(chunk)] += chunk
-    o = 128
-    while o:
-        s[:o] = s[:o] + s[o: 2 * o]
-        o //= 2
-    return s[0]
 
 
 def test_spectral_reduce_adds_in_the_documented_order():
